@@ -1,6 +1,9 @@
 """Rollout throughput bench: U-FNO twophase cfg, 256x256, 3 fields, obstacle (BASELINE.json config C3).
 
-python bench.py [--gpus N --steps K --warmup W]
+python bench.py [--gpus N --steps K --warmup W] [--full] [--dump-outputs DIR]
+  * a plain run sets up, warms up (W steps), times the K steps and prints the line; the roofline and
+    cpu_baseline legs below take runs of their own and run only with --full (null in the line otherwise);
+    --dump-outputs DIR writes what the last timed step returned as DIR/<name>.npy (dump_outputs);
   * one step = one autoregressive model call (advances tw=25 timesteps for every sample) plus the
     per-window MSE_sum loss, i.e. one iteration of AutoregressivePushforwardTrainer.simulate
     (reference trainers/autoregressivepushforwardtrainer.py:354-432), trajectory resident in HBM;
@@ -288,6 +291,35 @@ def timing_fields(elapsed, times, steps):
                 ms_per_step_per_rank=[round(t / steps * 1e3, 3) for t in times])
 
 
+DUMP_MAX_ELEMS = 1 << 22   # per array: 16 MiB of float32; a mode dumps at most three arrays (64 MB in all)
+DUMP_SEED = 20240607
+
+
+def dump_outputs(dirname, arrays, rank=0, world=1):
+    """--dump-outputs DIR: write what the last timed step returned, one DIR/<name>.npy per array (rank r of
+    N > 1 writes <name>_rank<r>.npy, its shard's).  float64 stays float64, everything else (bf16 included) is
+    written as float32; complex as its (re, im) pairs.  An array of more than DUMP_MAX_ELEMS elements is
+    written as a fixed sample of its flattened elements: indices torch.randint(0, numel, (DUMP_MAX_ELEMS,))
+    from a CPU generator seeded with DUMP_SEED, so two builds dump the same elements.  The inputs are seeded
+    (twophase_batch / torch.Generator), so the same arguments give the same inputs from run to run."""
+    import numpy as np
+    os.makedirs(dirname, exist_ok=True)
+    total = 0
+    for name, t in arrays.items():
+        t = t.detach()
+        if t.is_complex():
+            t = torch.view_as_real(t.resolve_conj())
+        if t.numel() > DUMP_MAX_ELEMS:
+            g = torch.Generator(device="cpu").manual_seed(DUMP_SEED)
+            idx = torch.randint(0, t.numel(), (DUMP_MAX_ELEMS,), generator=g)
+            t = t.reshape(-1)[idx.to(t.device)]
+        a = t.to(torch.float64 if t.dtype == torch.float64 else torch.float32).cpu().numpy()
+        total += a.nbytes
+        if total > 64 * 10 ** 6:
+            raise SystemExit(f"bench.py: --dump-outputs would write more than 64 MB ({name})")
+        np.save(os.path.join(dirname, name + (f"_rank{rank}" if world > 1 else "") + ".npy"), a)
+
+
 def cpu_baseline(model, ocfg, opde, res, num_c, calls=2, B=2):
     import oracle
     from trainers.synthetic import twophase_batch
@@ -338,6 +370,12 @@ def main():
                          "all-reduce + Adam (samples/s)")
     ap.add_argument("--launch-check", action="store_true",
                     help="bring the N ranks up (launcher, process group, shards), print them and exit; no GPU")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps also run the legs that take runs of their own: the live conv "
+                         "roofline probe, the CPU-oracle baseline with its GPU-vs-CPU rel-L2 (--cpu-calls) and the "
+                         "GPU figure at the CPU sample's batch; without it those fields of the line are null")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step returned to DIR/<name>.npy (see dump_outputs)")
     args = ap.parse_args()
     if args.gpus < 1:
         raise SystemExit("--gpus must be >= 1")
@@ -382,6 +420,12 @@ def main():
             return tr.simulate(u_all, cond, pos, compute_loss=True, include_data=False, nr_gt_steps=1,
                                t_res=tw * (nsteps + 1), spatial_conditioning=sc)
 
+    last = {}
+    if args.dump_outputs:
+        # simulate(include_data=False) returns the losses only: keep a reference to the model's latest output
+        # (the window the last timed step predicted) without touching the timed path
+        model.register_forward_hook(lambda mod, inp, out: last.__setitem__("pred", out))
+
     if args.warmup > 0:
         rollout(args.warmup)
     torch.cuda.synchronize()
@@ -398,12 +442,18 @@ def main():
     elapsed = max_over_ranks(mine, dev)
     times = per_rank_times(mine, dev)
     value = args.global_batch * tw * args.steps / elapsed
+    if args.dump_outputs:
+        # what simulate returned (one loss per timed step) and the last step's predicted window (B, num_c, tw, H, W)
+        dump_outputs(args.dump_outputs, {"losses": torch.stack(losses), "pred_last": last["pred"]}, rank, world)
 
     if rank == 0:
-        workload = dict(model=args.model, res=args.res, num_c=args.num_c, per_gpu_batch=B, fno_modes=args.fno_modes)
-        roof = attach_traffic(conv_roofline(model, u_all[:, :, :tw], cond, pos, sc), workload)
-        cpu = cpu_baseline(model, ocfg, opde, args.res, args.num_c, calls=args.cpu_calls) if (
-            args.cpu_calls > 0 and world == 1) else None
+        roof = cpu = None
+        if args.full:
+            workload = dict(model=args.model, res=args.res, num_c=args.num_c, per_gpu_batch=B,
+                            fno_modes=args.fno_modes)
+            roof = attach_traffic(conv_roofline(model, u_all[:, :, :tw], cond, pos, sc), workload)
+            if args.cpu_calls > 0 and world == 1:
+                cpu = cpu_baseline(model, ocfg, opde, args.res, args.num_c, calls=args.cpu_calls)
         if cpu is not None and B >= 2:
             # the north star's 10x is defined at the CPU sample's batch (B = 2): the same rollout on this
             # GPU at B = 2, timed like the headline
@@ -424,7 +474,7 @@ def main():
             "value": round(value, 3), "unit": "sample-timesteps/s", "n_gpus": world, "steps": args.steps,
             "warmup": args.warmup, **timing_fields(elapsed, times, args.steps), "higher_is_better": True,
             "scaling": "strong", "vs_baseline": None, "dtype": _dtype(), "data": "synthetic",
-            "dist": dist_info(world),
+            "dist": dist_info(world), "full": args.full,
             "config": {"workload": f"{args.model.upper()} twophase cfg rollout (simulate), {args.res}x{args.res}, "
                                    f"{args.num_c} fields, obstacle mask, tw=25", "model": args.model,
                        "global_batch": args.global_batch, "per_gpu_batch": B, "res": args.res,
@@ -499,6 +549,9 @@ def run_fno3d(args):
     mine = time.perf_counter() - t0
     elapsed = max_over_ranks(mine, dev)
     times = per_rank_times(mine, dev)
+    if args.dump_outputs:
+        # the processor's output of the last timed step: NDHWC (B, D, H, W, C) for ufno3d, (B, D*H, W, C) for fno3d
+        dump_outputs(args.dump_outputs, {"out_last": y}, rank, world)
     if rank == 0 and ufno:
         return print_ufno3d_line(args, m, step, hn, vn, gb, B, world, elapsed, times, bf16)
     if rank == 0:
@@ -536,9 +589,9 @@ def print_ufno3d_line(args, m, step, hn, vn, gb, B, world, elapsed, times, bf16)
     from models.common import to_ncdhw
     from nps_hip import ops
     D = C5_VOL[0]
-    roof = probe_roofline(step)
+    roof = probe_roofline(step) if args.full else None
     cpu = None
-    if args.cpu_calls > 0 and world == 1:
+    if args.full and args.cpu_calls > 0 and world == 1:
         threads = int(os.environ.get("OMP_NUM_THREADS", len(os.sched_getaffinity(0))))
         torch.set_num_threads(threads)
         sd = {k: v.detach().cpu() for k, v in m.state_dict().items() if k.split(".")[1] == "0"}
@@ -570,7 +623,7 @@ def print_ufno3d_line(args, m, step, hn, vn, gb, B, world, elapsed, times, bf16)
         "steps": args.steps, "warmup": args.warmup, **timing_fields(elapsed, times, args.steps),
         "higher_is_better": True, "scaling": "strong", "vs_baseline": None,
         "dtype": "bf16 storage, bf16 MFMA / fp32 accumulate" if bf16 else "f32", "data": "synthetic",
-        "dist": dist_info(world),
+        "dist": dist_info(world), "full": args.full,
         "config": {"workload": "U-FNO 3D (C5) over a 16x128x128 volume, 64 hidden + 4 cond, modes (8,12,12), "
                                "4 blocks, 3-D U-Nets ch_mults [1,1]", "model": "ufno3d", "global_batch": gb,
                    "per_gpu_batch": B, "parallelism": f"dp{world} (batch-sharded, no collective)"},
@@ -642,15 +695,21 @@ def run_train(args):
     times = per_rank_times(mine, dev)
     # the probe step runs on every rank: under a process group a training step holds collectives (the global
     # loss and the gradient all-reduce), which a rank-0-only step would leave unmatched
-    roof = probe_roofline(lambda: tr.train_one_epoch([batch], epoch=0))
+    if args.dump_outputs:
+        # what the last timed step returned (its loss) and left behind (the parameters after its Adam update)
+        flat = torch.cat([(torch.view_as_real(p) if p.is_complex() else p).detach().reshape(-1)
+                          for p in model.parameters()])
+        dump_outputs(args.dump_outputs, {"loss_last": torch.as_tensor(loss).detach().reshape(1), "params_last": flat},
+                     rank, world)
+    roof = probe_roofline(lambda: tr.train_one_epoch([batch], epoch=0)) if args.full else None
     if rank == 0:
-        cpu = cpu_baseline_train(model, args) if (args.cpu_calls > 0 and world == 1) else None
+        cpu = cpu_baseline_train(model, args) if (args.full and args.cpu_calls > 0 and world == 1) else None
         print(json.dumps({
             "metric": "pushforward training samples/sec (train_step + backward + all-reduce + Adam)",
             "value": round(args.global_batch * args.steps / elapsed, 3), "unit": "samples/s", "n_gpus": world,
             "steps": args.steps, "warmup": args.warmup, **timing_fields(elapsed, times, args.steps),
             "higher_is_better": True, "scaling": "strong", "vs_baseline": None, "dtype": _dtype(),
-            "data": "synthetic", "dist": dist_info(world),
+            "data": "synthetic", "dist": dist_info(world), "full": args.full,
             "config": {"workload": f"{args.model.upper()} twophase cfg train_step, {args.res}x{args.res}, "
                                    f"{args.num_c} fields, tw=25", "global_batch": args.global_batch,
                        "per_gpu_batch": B, "parallelism": f"dp{world} (RCCL gradient all-reduce)"},

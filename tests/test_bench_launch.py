@@ -54,3 +54,33 @@ def test_world_size_mismatch_exits_nonzero():
 def test_indivisible_batch_exits_nonzero():
     r = _bench(["--gpus", "3", "--launch-check"])
     assert r.returncode != 0
+
+
+def test_full_and_dump_outputs_are_options():
+    r = _bench(["--launch-check", "--full", "--dump-outputs", "unused"])
+    assert r.returncode == 0, r.stderr[-3000:]
+    assert _line(r.stdout)["dist"]["world_size"] == 1
+
+
+def test_dump_outputs_writes_float_arrays_and_a_fixed_sample(tmp_path):
+    """--dump-outputs: small arrays whole (shape kept; float64 stays, bf16 / complex become float32), an array
+    above DUMP_MAX_ELEMS as the same seeded sample of its elements on every call, rank-suffixed names at N > 1."""
+    import numpy as np
+    import torch
+    import bench
+    n = bench.DUMP_MAX_ELEMS + 12345
+    big = torch.arange(n, dtype=torch.float32)
+    arrays = {"small": torch.arange(6, dtype=torch.float64).reshape(2, 3), "half": torch.ones(4, dtype=torch.bfloat16),
+              "cplx": torch.tensor([1 + 2j, 3 - 4j], dtype=torch.complex64), "big": big}
+    bench.dump_outputs(str(tmp_path / "a"), arrays)
+    bench.dump_outputs(str(tmp_path / "b"), {"big": big * 2}, rank=1, world=2)
+    got = {k: np.load(tmp_path / "a" / f"{k}.npy") for k in arrays}
+    assert got["small"].dtype == np.float64 and got["small"].shape == (2, 3)
+    assert got["half"].dtype == np.float32 and got["cplx"].dtype == np.float32
+    assert got["cplx"].tolist() == [[1.0, 2.0], [3.0, -4.0]]
+    assert got["big"].dtype == np.float32 and got["big"].shape == (bench.DUMP_MAX_ELEMS,)
+    assert sum(a.nbytes for a in got.values()) <= 64 * 10 ** 6
+    # values of `big` are their own indices: the sample is in range, not constant, and the same on every call
+    assert got["big"].min() >= 0 and got["big"].max() < n and len(np.unique(got["big"][:1000])) > 900
+    other = np.load(tmp_path / "b" / "big_rank1.npy")
+    assert np.array_equal(other, 2 * got["big"])

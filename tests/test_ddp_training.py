@@ -192,6 +192,10 @@ def test_torchrun_train_py_without_wrapper(tmp_path):
     env = dict(os.environ, OMP_NUM_THREADS="1")
     for k in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "NPS_AUTO_DIST"):
         env.pop(k, None)
+    if torch.cuda.is_available():
+        # where a GPU is visible the launch hook would pick RCCL with one card per rank; this scenario is the CPU
+        # one (two gloo ranks, model on the host) on every machine, a one-GPU box included
+        env["NPS_DIST_BACKEND"] = "gloo"
     r = subprocess.run([sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node=2",
                         "--master-addr", "127.0.0.1", "--master-port", str(port),
                         os.path.join(ROOT, "tests", "ddp_torchrun_scenario.py"), str(tmp_path)],

@@ -20,9 +20,10 @@ for r in $(seq 1 $ROUNDS); do
       *) F=$LIBDIR/$L ;;
     esac
     [ -f "$F" ] || { echo "missing $F"; exit 1; }
-    env $EV NPS_HIP_LIB=$PWD/$F timeout -k 10 300 python3 bench.py --cpu-calls 0 "$@" > gpurun_out/${TAG}_one.json 2> gpurun_out/${TAG}_one.err \
-      || { echo "bench failed on $L"; tail -20 gpurun_out/${TAG}_one.err; exit 1; }
-    python3 - "$L" gpurun_out/${TAG}_one.json >> $O <<'EOF'
+    ONE=${O%_ab.jsonl}_one   # this run's line, next to the summary; --full: the roofline fields read below
+    env $EV NPS_HIP_LIB=$PWD/$F timeout -k 10 300 python3 bench.py --full --cpu-calls 0 "$@" > $ONE.json 2> $ONE.err \
+      || { echo "bench failed on $L"; tail -20 $ONE.err; exit 1; }
+    python3 - "$L" $ONE.json >> $O <<'EOF'
 import json, sys
 d = json.loads(open(sys.argv[2]).read().strip().splitlines()[-1])
 r = d.get("roofline") or {}
