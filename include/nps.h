@@ -261,6 +261,14 @@ int nps_spectral_idft_h(const float* Y, float* Z, int B, int H, int m1, int m2, 
  * output's range tag, raised to cover every value written (nps_conv2d_t.out_tag) */
 int nps_spectral_idft_w(const float* Z, float* out, int B, int H, int W, int m2, int Cout, int accumulate,
                         const float* addend, int act, float* out_tag, void* stream);
+/* The two W passes on channels-first activations (the reference modules' own layout): x / out are [B][C][H][W]
+ * with W contiguous, plane stride H*W and a batch stride `*_bs` in elements (0 = dense, else >= C*H*W: a channel
+ * slice of a larger NCHW tensor, e.g. one operand of a torch.cat, is passed as it lies).  NCDHW is the same view
+ * with H = D*H.  Only 4-byte alignment is assumed.  X1 / Z keep the layouts above, so every stage between the W
+ * passes is shared.  No addend and no range tag. */
+int nps_spectral_dft_w_nchw(const float* x, long x_bs, int B, int H, int W, int C, int m2, float* X1, void* stream);
+int nps_spectral_idft_w_nchw(const float* Z, float* out, long out_bs, int B, int H, int W, int m2, int Cout,
+                             int accumulate, int act, void* stream);
 
 /* ---- one call per module: SpectralConv2d / SpectralConv3d / FNO_Layer (composites of the stages) ------
  * The stage entry points above and below, sequenced inside the library, so a C caller runs a whole module
@@ -296,6 +304,25 @@ int nps_spectral_conv3d_fwd(const float* x, const float* w1, const float* w2, co
 int nps_spectral_conv3d_bwd(const float* x, const float* w1, const float* w2, const float* w3, const float* w4,
                             const float* dy, float* dx, float* dw1, float* dw2, float* dw3, float* dw4, void* ws,
                             int B, int Cin, int Cout, int D, int H, int W, int m1, int m2, int m3, void* stream);
+/* The same four calls on the reference modules' own channels-first tensors: x / y / dy / dx are fp32 NCHW
+ * ([B][C][H][W]; 3-D: NCDHW), each with a batch stride in elements (0 = dense, else >= C*H*W resp. C*D*H*W, so a
+ * channel slice of a larger tensor needs no copy; a smaller or negative stride is an error).  Semantics, error
+ * codes and mode bounds are those of the NHWC calls (dx == NULL skips dx, dw all or none).  The intermediates are
+ * layout-independent, so nps_spectral_conv2d_workspace / nps_spectral_conv3d_workspace size `ws` for both
+ * layouts.  y must not alias x (y is written while other rows of x are still being read). */
+int nps_spectral_conv2d_fwd_nchw(const float* x, long x_bs, const float* w1, const float* w2, float* y, long y_bs,
+                                 void* ws, int B, int Cin, int Cout, int H, int W, int m1, int m2, int accumulate,
+                                 int act, void* stream);
+int nps_spectral_conv2d_bwd_nchw(const float* x, long x_bs, const float* w1, const float* w2, const float* dy,
+                                 long dy_bs, float* dx, long dx_bs, float* dw1, float* dw2, void* ws, int B, int Cin,
+                                 int Cout, int H, int W, int m1, int m2, void* stream);
+int nps_spectral_conv3d_fwd_nchw(const float* x, long x_bs, const float* w1, const float* w2, const float* w3,
+                                 const float* w4, float* y, long y_bs, void* ws, int B, int Cin, int Cout, int D, int H,
+                                 int W, int m1, int m2, int m3, int accumulate, int act, void* stream);
+int nps_spectral_conv3d_bwd_nchw(const float* x, long x_bs, const float* w1, const float* w2, const float* w3,
+                                 const float* w4, const float* dy, long dy_bs, float* dx, long dx_bs, float* dw1,
+                                 float* dw2, float* dw3, float* dw4, void* ws, int B, int Cin, int Cout, int D, int H,
+                                 int W, int m1, int m2, int m3, void* stream);
 
 /* ---- bf16 storage (BASELINE config C5: the 3-D rFFT spectral conv in bf16) ----------------------------
  * Activations in HBM as bf16 (16-bit storage of NDHWC tensors viewed as (B, D*H, W, C)), every sum in fp32:
@@ -433,6 +460,12 @@ int nps_scaled_diff(const float* a, const float* b, const double* scale, float* 
  *  gweights1/2 = unpack_grad(gwpack)  (PyTorch's complex-gradient convention, conj(x) * g) */
 int nps_spectral_idft_w_bwd(const float* gy, float* gZ, int B, int H, int W, int m2, int Cout, void* stream);
 int nps_spectral_dft_w_bwd(const float* gX1, float* gx, int B, int H, int W, int m2, int Cin, void* stream);
+/* the same two adjoint W passes reading gy / writing gx channels-first (layout and batch stride as
+ * nps_spectral_dft_w_nchw) */
+int nps_spectral_idft_w_bwd_nchw(const float* gy, long gy_bs, float* gZ, int B, int H, int W, int m2, int Cout,
+                                 void* stream);
+int nps_spectral_dft_w_bwd_nchw(const float* gX1, float* gx, long gx_bs, int B, int H, int W, int m2, int Cin,
+                                void* stream);
 int nps_spectral_mix_bwd(const float* X2, const float* wpack, const float* gY, float* gX2, float* gwpack, int B,
                          int R, int m2, int Cin, int Cout, void* stream);
 int nps_spectral_unpack_grad(const float* gwpack, float* gw1, float* gw2, int Cin, int Cout, int H, int m1, int m2,

@@ -48,8 +48,36 @@ bool spec2_args_ok(int B, int Cin, int Cout, int H, int W, int m1, int m2) {
     return B > 0 && Cin > 0 && Cout > 0 && H > 0 && W > 0 && m1 > 0 && m2 > 0 && m1 <= H && m2 <= W / 2 + 1;
 }
 
-// Z = the spectral conv up to its W-pass synthesis, for the frame `src` (nsrc sources covering B x H x W x Cin)
-int spec2_z(const nps_src_t* src, int nsrc, const float* w1, const float* w2, Carve& c, const Spec2& sz, int B,
+// Layout of a composite's activation operand: NHWC [B][R][W][C] (dense), or channels-first [B][C][R][W] with a batch
+// stride in elements (0 = dense).  Only the W passes see it; R = H, or D*H in 3-D.
+struct Lay {
+    bool nchw;
+    long bs;
+};
+constexpr Lay NHWC = {false, 0};
+
+bool stride_ok(long bs, long per_batch) { return bs == 0 || bs >= per_batch; }
+
+int w_dft(const nps_src_t* src, int nsrc, Lay l, int B, int R, int W, int C, int m, float* X1, void* s) {
+    if (l.nchw) return nps_spectral_dft_w_nchw(src[0].ptr, l.bs, B, R, W, C, m, X1, s);
+    return nps_spectral_dft_w(src, nsrc, B, R, W, C, m, X1, s);
+}
+int w_idft(const float* Z, float* y, Lay l, int B, int R, int W, int m, int Cout, int accumulate, int act, void* s) {
+    if (l.nchw) return nps_spectral_idft_w_nchw(Z, y, l.bs, B, R, W, m, Cout, accumulate, act, s);
+    return nps_spectral_idft_w(Z, y, B, R, W, m, Cout, accumulate, nullptr, act, nullptr, s);
+}
+int w_idft_bwd(const float* dy, Lay l, float* gZ, int B, int R, int W, int m, int Cout, void* s) {
+    if (l.nchw) return nps_spectral_idft_w_bwd_nchw(dy, l.bs, gZ, B, R, W, m, Cout, s);
+    return nps_spectral_idft_w_bwd(dy, gZ, B, R, W, m, Cout, s);
+}
+int w_dft_bwd(const float* gX1, float* dx, Lay l, int B, int R, int W, int m, int Cin, void* s) {
+    if (l.nchw) return nps_spectral_dft_w_bwd_nchw(gX1, dx, l.bs, B, R, W, m, Cin, s);
+    return nps_spectral_dft_w_bwd(gX1, dx, B, R, W, m, Cin, s);
+}
+
+// Z = the spectral conv up to its W-pass synthesis, for the frame `src` (nsrc sources covering B x H x W x Cin; one
+// channels-first tensor when xl.nchw)
+int spec2_z(const nps_src_t* src, int nsrc, Lay xl, const float* w1, const float* w2, Carve& c, const Spec2& sz, int B,
             int Cin, int Cout, int H, int W, int m1, int m2, float** Zout, float** X2out, float** wpout, void* s) {
     const int R = H < 2 * m1 ? H : 2 * m1;
     float* wp = c.take(sz.wp);
@@ -59,7 +87,7 @@ int spec2_z(const nps_src_t* src, int nsrc, const float* w1, const float* w2, Ca
     float* Z = c.take(sz.z);
     int rc;
     if ((rc = nps_spectral_pack_weights(w1, w2, wp, Cin, Cout, H, m1, m2, s)) < 0) return rc;
-    if ((rc = nps_spectral_dft_w(src, nsrc, B, H, W, Cin, m2, X1, s)) < 0) return rc;
+    if ((rc = w_dft(src, nsrc, xl, B, H, W, Cin, m2, X1, s)) < 0) return rc;
     if ((rc = nps_spectral_dft_h(X1, X2, B, H, m1, m2, Cin, s)) < 0) return rc;
     if ((rc = nps_spectral_mix(X2, wp, Y, B, R, m2, Cin, Cout, s)) < 0) return rc;
     if ((rc = nps_spectral_idft_h(Y, Z, B, H, m1, m2, Cout, s)) < 0) return rc;
@@ -112,30 +140,40 @@ extern "C" size_t nps_spectral_conv2d_workspace(int B, int Cin, int Cout, int H,
     return spec2_ws(B, Cin, Cout, H, m1, m2);
 }
 
-extern "C" int nps_spectral_conv2d_fwd(const float* x, const float* w1, const float* w2, float* y, void* ws, int B,
-                                       int Cin, int Cout, int H, int W, int m1, int m2, int accumulate, int act,
-                                       void* stream) {
-    NPS_CHECK_ARG(x && w1 && w2 && y && ws, "spectral_conv2d_fwd: NULL pointer");
+namespace {
+
+// The 2-D composites for either layout (`what` names the entry point in the error text)
+int conv2d_fwd(const char* what, const float* x, Lay xl, const float* w1, const float* w2, float* y, Lay yl, void* ws,
+               int B, int Cin, int Cout, int H, int W, int m1, int m2, int accumulate, int act, void* stream) {
+    NPS_CHECK_ARG(x && w1 && w2 && y && ws, "%s: NULL pointer", what);
     NPS_CHECK_ARG(spec2_args_ok(B, Cin, Cout, H, W, m1, m2),
-                  "spectral_conv2d_fwd: modes should be at most the spatial dim (// 2 + 1 for the last spatial "
-                  "dimension) (H=%d W=%d m1=%d m2=%d)", H, W, m1, m2);
-    NPS_CHECK_ARG(act == 0 || act == 1, "spectral_conv2d_fwd: act is 0 (none) or 1 (GELU)");
+                  "%s: modes should be at most the spatial dim (// 2 + 1 for the last spatial "
+                  "dimension) (H=%d W=%d m1=%d m2=%d)", what, H, W, m1, m2);
+    NPS_CHECK_ARG(act == 0 || act == 1, "%s: act is 0 (none) or 1 (GELU)", what);
+    NPS_CHECK_ARG(stride_ok(xl.bs, (long)Cin * H * W) && stride_ok(yl.bs, (long)Cout * H * W),
+                  "%s: a batch stride is negative or smaller than C*H*W elements (x_bs=%ld, Cin*H*W=%ld; y_bs=%ld, "
+                  "Cout*H*W=%ld; 0 = dense)", what, xl.bs, (long)Cin * H * W, yl.bs, (long)Cout * H * W);
     const nps_src_t src = {x, Cin, H, W, 0, 0};
     Carve c{static_cast<char*>(ws)};
     const Spec2 sz = spec2_sizes(B, Cin, Cout, H, m1, m2);
     float* Z = nullptr;
-    int rc = spec2_z(&src, 1, w1, w2, c, sz, B, Cin, Cout, H, W, m1, m2, &Z, nullptr, nullptr, stream);
+    int rc = spec2_z(&src, 1, xl, w1, w2, c, sz, B, Cin, Cout, H, W, m1, m2, &Z, nullptr, nullptr, stream);
     if (rc < 0) return rc;
-    return nps_spectral_idft_w(Z, y, B, H, W, m2, Cout, accumulate ? 1 : 0, nullptr, act, nullptr, stream);
+    return w_idft(Z, y, yl, B, H, W, m2, Cout, accumulate ? 1 : 0, act, stream);
 }
 
-extern "C" int nps_spectral_conv2d_bwd(const float* x, const float* w1, const float* w2, const float* dy, float* dx,
-                                       float* dw1, float* dw2, void* ws, int B, int Cin, int Cout, int H, int W,
-                                       int m1, int m2, void* stream) {
-    NPS_CHECK_ARG(x && w1 && w2 && dy && ws, "spectral_conv2d_bwd: NULL pointer");
-    NPS_CHECK_ARG((dw1 == nullptr) == (dw2 == nullptr), "spectral_conv2d_bwd: dw1 and dw2 are both given or both NULL");
-    NPS_CHECK_ARG(spec2_args_ok(B, Cin, Cout, H, W, m1, m2), "spectral_conv2d_bwd: bad shape (H=%d W=%d m1=%d m2=%d)",
-                  H, W, m1, m2);
+int conv2d_bwd(const char* what, const float* x, Lay xl, const float* w1, const float* w2, const float* dy, Lay dyl,
+               float* dx, Lay dxl, float* dw1, float* dw2, void* ws, int B, int Cin, int Cout, int H, int W, int m1,
+               int m2, void* stream) {
+    NPS_CHECK_ARG(x && w1 && w2 && dy && ws, "%s: NULL pointer", what);
+    NPS_CHECK_ARG((dw1 == nullptr) == (dw2 == nullptr), "%s: dw1 and dw2 are both given or both NULL", what);
+    NPS_CHECK_ARG(spec2_args_ok(B, Cin, Cout, H, W, m1, m2), "%s: bad shape (H=%d W=%d m1=%d m2=%d)", what, H, W, m1,
+                  m2);
+    NPS_CHECK_ARG(stride_ok(xl.bs, (long)Cin * H * W) && stride_ok(dxl.bs, (long)Cin * H * W) &&
+                      stride_ok(dyl.bs, (long)Cout * H * W),
+                  "%s: a batch stride is negative or smaller than C*H*W elements (x_bs=%ld dx_bs=%ld, Cin*H*W=%ld; "
+                  "dy_bs=%ld, Cout*H*W=%ld; 0 = dense)", what, xl.bs, dxl.bs, (long)Cin * H * W, dyl.bs,
+                  (long)Cout * H * W);
     const int R = H < 2 * m1 ? H : 2 * m1;
     const Spec2 sz = spec2_sizes(B, Cin, Cout, H, m1, m2);
     Carve c{static_cast<char*>(ws)};
@@ -150,19 +188,50 @@ extern "C" int nps_spectral_conv2d_bwd(const float* x, const float* w1, const fl
     int rc;
     // the forward's retained spectrum X2 (mix_bwd's conj(X2) for the weight gradient) and the packed weight
     if ((rc = nps_spectral_pack_weights(w1, w2, wp, Cin, Cout, H, m1, m2, stream)) < 0) return rc;
-    if ((rc = nps_spectral_dft_w(&src, 1, B, H, W, Cin, m2, X1, stream)) < 0) return rc;
+    if ((rc = w_dft(&src, 1, xl, B, H, W, Cin, m2, X1, stream)) < 0) return rc;
     if ((rc = nps_spectral_dft_h(X1, X2, B, H, m1, m2, Cin, stream)) < 0) return rc;
     // adjoint chain: irfft2's adjoint, the H pass, the mixing's two adjoint products
-    if ((rc = nps_spectral_idft_w_bwd(dy, gZ, B, H, W, m2, Cout, stream)) < 0) return rc;
+    if ((rc = w_idft_bwd(dy, dyl, gZ, B, H, W, m2, Cout, stream)) < 0) return rc;
     if ((rc = nps_spectral_dft_h(gZ, gY, B, H, m1, m2, Cout, stream)) < 0) return rc;
     if ((rc = nps_spectral_mix_bwd(X2, wp, gY, gX2, gwp, B, R, m2, Cin, Cout, stream)) < 0) return rc;
     if (dx != nullptr) {
         if ((rc = nps_spectral_idft_h(gX2, X1, B, H, m1, m2, Cin, stream)) < 0) return rc;
-        if ((rc = nps_spectral_dft_w_bwd(X1, dx, B, H, W, m2, Cin, stream)) < 0) return rc;
+        if ((rc = w_dft_bwd(X1, dx, dxl, B, H, W, m2, Cin, stream)) < 0) return rc;
     }
     if (dw1 != nullptr)
         if ((rc = nps_spectral_unpack_grad(gwp, dw1, dw2, Cin, Cout, H, m1, m2, stream)) < 0) return rc;
     return 0;
+}
+
+}  // namespace
+
+extern "C" int nps_spectral_conv2d_fwd(const float* x, const float* w1, const float* w2, float* y, void* ws, int B,
+                                       int Cin, int Cout, int H, int W, int m1, int m2, int accumulate, int act,
+                                       void* stream) {
+    return conv2d_fwd("spectral_conv2d_fwd", x, NHWC, w1, w2, y, NHWC, ws, B, Cin, Cout, H, W, m1, m2, accumulate, act,
+                      stream);
+}
+
+extern "C" int nps_spectral_conv2d_fwd_nchw(const float* x, long x_bs, const float* w1, const float* w2, float* y,
+                                            long y_bs, void* ws, int B, int Cin, int Cout, int H, int W, int m1,
+                                            int m2, int accumulate, int act, void* stream) {
+    return conv2d_fwd("spectral_conv2d_fwd_nchw", x, Lay{true, x_bs}, w1, w2, y, Lay{true, y_bs}, ws, B, Cin, Cout, H,
+                      W, m1, m2, accumulate, act, stream);
+}
+
+extern "C" int nps_spectral_conv2d_bwd(const float* x, const float* w1, const float* w2, const float* dy, float* dx,
+                                       float* dw1, float* dw2, void* ws, int B, int Cin, int Cout, int H, int W,
+                                       int m1, int m2, void* stream) {
+    return conv2d_bwd("spectral_conv2d_bwd", x, NHWC, w1, w2, dy, NHWC, dx, NHWC, dw1, dw2, ws, B, Cin, Cout, H, W, m1,
+                      m2, stream);
+}
+
+extern "C" int nps_spectral_conv2d_bwd_nchw(const float* x, long x_bs, const float* w1, const float* w2,
+                                            const float* dy, long dy_bs, float* dx, long dx_bs, float* dw1,
+                                            float* dw2, void* ws, int B, int Cin, int Cout, int H, int W, int m1,
+                                            int m2, void* stream) {
+    return conv2d_bwd("spectral_conv2d_bwd_nchw", x, Lay{true, x_bs}, w1, w2, dy, Lay{true, dy_bs}, dx,
+                      Lay{true, dx_bs}, dw1, dw2, ws, B, Cin, Cout, H, W, m1, m2, stream);
 }
 
 extern "C" size_t nps_fno_layer2d_workspace(int B, int Cin, int Cout, int H, int W, int m1, int m2) {
@@ -183,7 +252,7 @@ extern "C" int nps_fno_layer2d_fwd(const nps_conv2d_t* w, const float* w1, const
     Carve c{static_cast<char*>(ws)};
     const Spec2 sz = spec2_sizes(B, Cin, Cout, H, m1, m2);
     float* Z = nullptr;
-    int rc = spec2_z(a.src, a.nsrc, w1, w2, c, sz, B, Cin, Cout, H, W, m1, m2, &Z, nullptr, nullptr, stream);
+    int rc = spec2_z(a.src, a.nsrc, NHWC, w1, w2, c, sz, B, Cin, Cout, H, W, m1, m2, &Z, nullptr, nullptr, stream);
     if (rc < 0) return rc;
     nps_conv2d_t f = a;
     if (fno_fusable(a, m2)) {
@@ -208,14 +277,20 @@ extern "C" size_t nps_spectral_conv3d_workspace(int B, int Cin, int Cout, int D,
     return spec3_ws(B, Cin, Cout, D, H, m1, m2, m3);
 }
 
-extern "C" int nps_spectral_conv3d_fwd(const float* x, const float* w1, const float* w2, const float* w3,
-                                       const float* w4, float* y, void* ws, int B, int Cin, int Cout, int D, int H,
-                                       int W, int m1, int m2, int m3, int accumulate, int act, void* stream) {
-    NPS_CHECK_ARG(x && w1 && w2 && w3 && w4 && y && ws, "spectral_conv3d_fwd: NULL pointer");
+namespace {
+
+int conv3d_fwd(const char* what, const float* x, Lay xl, const float* w1, const float* w2, const float* w3,
+               const float* w4, float* y, Lay yl, void* ws, int B, int Cin, int Cout, int D, int H, int W, int m1,
+               int m2, int m3, int accumulate, int act, void* stream) {
+    NPS_CHECK_ARG(x && w1 && w2 && w3 && w4 && y && ws, "%s: NULL pointer", what);
     NPS_CHECK_ARG(spec3_args_ok(B, Cin, Cout, D, H, W, m1, m2, m3),
-                  "spectral_conv3d_fwd: modes should be at most the spatial dim (// 2 + 1 for the last spatial "
-                  "dimension) (D=%d H=%d W=%d m=%d,%d,%d)", D, H, W, m1, m2, m3);
-    NPS_CHECK_ARG(act == 0 || act == 1, "spectral_conv3d_fwd: act is 0 (none) or 1 (GELU)");
+                  "%s: modes should be at most the spatial dim (// 2 + 1 for the last spatial "
+                  "dimension) (D=%d H=%d W=%d m=%d,%d,%d)", what, D, H, W, m1, m2, m3);
+    NPS_CHECK_ARG(act == 0 || act == 1, "%s: act is 0 (none) or 1 (GELU)", what);
+    NPS_CHECK_ARG(stride_ok(xl.bs, (long)Cin * D * H * W) && stride_ok(yl.bs, (long)Cout * D * H * W),
+                  "%s: a batch stride is negative or smaller than C*D*H*W elements (x_bs=%ld, Cin*D*H*W=%ld; "
+                  "y_bs=%ld, Cout*D*H*W=%ld; 0 = dense)", what, xl.bs, (long)Cin * D * H * W, yl.bs,
+                  (long)Cout * D * H * W);
     const int R1 = D < 2 * m1 ? D : 2 * m1, R2 = H < 2 * m2 ? H : 2 * m2;
     const Spec3 sz = spec3_sizes(B, Cin, Cout, D, H, m1, m2, m3);
     Carve c{static_cast<char*>(ws)};
@@ -226,27 +301,32 @@ extern "C" int nps_spectral_conv3d_fwd(const float* x, const float* w1, const fl
     float* Y = c.take(sz.y);
     float* Z1 = c.take(sz.z1);
     float* Z2 = c.take(sz.z2);
-    const nps_src_t src = {x, Cin, D * H, W, 0, 0};  // NDHWC viewed as (B, D*H, W, C)
+    const nps_src_t src = {x, Cin, D * H, W, 0, 0};  // NDHWC viewed as (B, D*H, W, C); NCDHW as (B, C, D*H, W)
     int rc;
     if ((rc = nps_spectral3d_pack_weights(w1, w2, w3, w4, wp, Cin, Cout, D, H, m1, m2, m3, stream)) < 0) return rc;
-    if ((rc = nps_spectral_dft_w(&src, 1, B, D * H, W, Cin, m3, X1, stream)) < 0) return rc;
+    if ((rc = w_dft(&src, 1, xl, B, D * H, W, Cin, m3, X1, stream)) < 0) return rc;
     if ((rc = nps_spectral_dft_h(X1, X2, B * D, H, m2, m3, Cin, stream)) < 0) return rc;
     if ((rc = nps_spectral_dft_h(X2, X3, B, D, m1, R2 * m3, Cin, stream)) < 0) return rc;
     if ((rc = nps_spectral_mix(X3, wp, Y, B, R1, R2 * m3, Cin, Cout, stream)) < 0) return rc;
     if ((rc = nps_spectral_idft_h(Y, Z1, B, D, m1, R2 * m3, Cout, stream)) < 0) return rc;
     if ((rc = nps_spectral_idft_h(Z1, Z2, B * D, H, m2, m3, Cout, stream)) < 0) return rc;
-    return nps_spectral_idft_w(Z2, y, B, D * H, W, m3, Cout, accumulate ? 1 : 0, nullptr, act, nullptr, stream);
+    return w_idft(Z2, y, yl, B, D * H, W, m3, Cout, accumulate ? 1 : 0, act, stream);
 }
 
-extern "C" int nps_spectral_conv3d_bwd(const float* x, const float* w1, const float* w2, const float* w3,
-                                       const float* w4, const float* dy, float* dx, float* dw1, float* dw2,
-                                       float* dw3, float* dw4, void* ws, int B, int Cin, int Cout, int D, int H, int W,
-                                       int m1, int m2, int m3, void* stream) {
-    NPS_CHECK_ARG(x && w1 && w2 && w3 && w4 && dy && ws, "spectral_conv3d_bwd: NULL pointer");
+int conv3d_bwd(const char* what, const float* x, Lay xl, const float* w1, const float* w2, const float* w3,
+               const float* w4, const float* dy, Lay dyl, float* dx, Lay dxl, float* dw1, float* dw2, float* dw3,
+               float* dw4, void* ws, int B, int Cin, int Cout, int D, int H, int W, int m1, int m2, int m3,
+               void* stream) {
+    NPS_CHECK_ARG(x && w1 && w2 && w3 && w4 && dy && ws, "%s: NULL pointer", what);
     const bool gw = dw1 != nullptr;
     NPS_CHECK_ARG((dw2 != nullptr) == gw && (dw3 != nullptr) == gw && (dw4 != nullptr) == gw,
-                  "spectral_conv3d_bwd: dw1..dw4 are all given or all NULL");
-    NPS_CHECK_ARG(spec3_args_ok(B, Cin, Cout, D, H, W, m1, m2, m3), "spectral_conv3d_bwd: bad shape");
+                  "%s: dw1..dw4 are all given or all NULL", what);
+    NPS_CHECK_ARG(spec3_args_ok(B, Cin, Cout, D, H, W, m1, m2, m3), "%s: bad shape", what);
+    NPS_CHECK_ARG(stride_ok(xl.bs, (long)Cin * D * H * W) && stride_ok(dxl.bs, (long)Cin * D * H * W) &&
+                      stride_ok(dyl.bs, (long)Cout * D * H * W),
+                  "%s: a batch stride is negative or smaller than C*D*H*W elements (x_bs=%ld dx_bs=%ld, "
+                  "Cin*D*H*W=%ld; dy_bs=%ld, Cout*D*H*W=%ld; 0 = dense)", what, xl.bs, dxl.bs, (long)Cin * D * H * W,
+                  dyl.bs, (long)Cout * D * H * W);
     const int R1 = D < 2 * m1 ? D : 2 * m1, R2 = H < 2 * m2 ? H : 2 * m2;
     const Spec3 sz = spec3_sizes(B, Cin, Cout, D, H, m1, m2, m3);
     Carve c{static_cast<char*>(ws)};
@@ -262,20 +342,54 @@ extern "C" int nps_spectral_conv3d_bwd(const float* x, const float* w1, const fl
     const nps_src_t src = {x, Cin, D * H, W, 0, 0};
     int rc;
     if ((rc = nps_spectral3d_pack_weights(w1, w2, w3, w4, wp, Cin, Cout, D, H, m1, m2, m3, stream)) < 0) return rc;
-    if ((rc = nps_spectral_dft_w(&src, 1, B, D * H, W, Cin, m3, X1, stream)) < 0) return rc;
+    if ((rc = w_dft(&src, 1, xl, B, D * H, W, Cin, m3, X1, stream)) < 0) return rc;
     if ((rc = nps_spectral_dft_h(X1, X2, B * D, H, m2, m3, Cin, stream)) < 0) return rc;
     if ((rc = nps_spectral_dft_h(X2, X3, B, D, m1, R2 * m3, Cin, stream)) < 0) return rc;
-    if ((rc = nps_spectral_idft_w_bwd(dy, gZ2, B, D * H, W, m3, Cout, stream)) < 0) return rc;
+    if ((rc = w_idft_bwd(dy, dyl, gZ2, B, D * H, W, m3, Cout, stream)) < 0) return rc;
     if ((rc = nps_spectral_dft_h(gZ2, gZ1, B * D, H, m2, m3, Cout, stream)) < 0) return rc;
     if ((rc = nps_spectral_dft_h(gZ1, gY, B, D, m1, R2 * m3, Cout, stream)) < 0) return rc;
     if ((rc = nps_spectral_mix_bwd(X3, wp, gY, gX3, gwp, B, R1, R2 * m3, Cin, Cout, stream)) < 0) return rc;
     if (dx != nullptr) {
         if ((rc = nps_spectral_idft_h(gX3, X2, B, D, m1, R2 * m3, Cin, stream)) < 0) return rc;
         if ((rc = nps_spectral_idft_h(X2, X1, B * D, H, m2, m3, Cin, stream)) < 0) return rc;
-        if ((rc = nps_spectral_dft_w_bwd(X1, dx, B, D * H, W, m3, Cin, stream)) < 0) return rc;
+        if ((rc = w_dft_bwd(X1, dx, dxl, B, D * H, W, m3, Cin, stream)) < 0) return rc;
     }
     if (gw)
         if ((rc = nps_spectral3d_unpack_grad(gwp, dw1, dw2, dw3, dw4, Cin, Cout, D, H, m1, m2, m3, stream)) < 0)
             return rc;
     return 0;
+}
+
+}  // namespace
+
+extern "C" int nps_spectral_conv3d_fwd(const float* x, const float* w1, const float* w2, const float* w3,
+                                       const float* w4, float* y, void* ws, int B, int Cin, int Cout, int D, int H,
+                                       int W, int m1, int m2, int m3, int accumulate, int act, void* stream) {
+    return conv3d_fwd("spectral_conv3d_fwd", x, NHWC, w1, w2, w3, w4, y, NHWC, ws, B, Cin, Cout, D, H, W, m1, m2, m3,
+                      accumulate, act, stream);
+}
+
+extern "C" int nps_spectral_conv3d_fwd_nchw(const float* x, long x_bs, const float* w1, const float* w2,
+                                            const float* w3, const float* w4, float* y, long y_bs, void* ws, int B,
+                                            int Cin, int Cout, int D, int H, int W, int m1, int m2, int m3,
+                                            int accumulate, int act, void* stream) {
+    return conv3d_fwd("spectral_conv3d_fwd_nchw", x, Lay{true, x_bs}, w1, w2, w3, w4, y, Lay{true, y_bs}, ws, B, Cin,
+                      Cout, D, H, W, m1, m2, m3, accumulate, act, stream);
+}
+
+extern "C" int nps_spectral_conv3d_bwd(const float* x, const float* w1, const float* w2, const float* w3,
+                                       const float* w4, const float* dy, float* dx, float* dw1, float* dw2,
+                                       float* dw3, float* dw4, void* ws, int B, int Cin, int Cout, int D, int H, int W,
+                                       int m1, int m2, int m3, void* stream) {
+    return conv3d_bwd("spectral_conv3d_bwd", x, NHWC, w1, w2, w3, w4, dy, NHWC, dx, NHWC, dw1, dw2, dw3, dw4, ws, B,
+                      Cin, Cout, D, H, W, m1, m2, m3, stream);
+}
+
+extern "C" int nps_spectral_conv3d_bwd_nchw(const float* x, long x_bs, const float* w1, const float* w2,
+                                            const float* w3, const float* w4, const float* dy, long dy_bs, float* dx,
+                                            long dx_bs, float* dw1, float* dw2, float* dw3, float* dw4, void* ws,
+                                            int B, int Cin, int Cout, int D, int H, int W, int m1, int m2, int m3,
+                                            void* stream) {
+    return conv3d_bwd("spectral_conv3d_bwd_nchw", x, Lay{true, x_bs}, w1, w2, w3, w4, dy, Lay{true, dy_bs}, dx,
+                      Lay{true, dx_bs}, dw1, dw2, dw3, dw4, ws, B, Cin, Cout, D, H, W, m1, m2, m3, stream);
 }

@@ -261,14 +261,13 @@ class SpectralConv2d(nn.Module):
     def forward(self, x, p=None):
         if self.feature_transform:
             raise NotImplementedError("FiLM spectral conditioning is not on the MI355X path")
+        # the module's own NCHW tensors go straight to the channels-first W passes: no layout round trip
+        H, W = x.shape[2:4]
+        if not (self.modes1 <= H and self.modes2 <= W // 2 + 1):
+            raise AssertionError("modes should be at most the spatial dim (// 2 + 1 for the last spatial dimension)")
         if use_autograd(self):
-            x = ad.to_nhwc(x)
-            H, W = x.shape[1:3]
-            if not (self.modes1 <= H and self.modes2 <= W // 2 + 1):
-                raise AssertionError("modes should be at most the spatial dim (// 2 + 1 for the last spatial dimension)")
-            return ad.to_nchw(ad.spectral_conv2d(self, x))
-        x = ops.nchw_to_nhwc(x)
-        return ops.nhwc_to_nchw(self.run([ops.Src(x)]))
+            return ad.spectral_conv2d_nchw(self, x)
+        return ops.spectral_conv2d_nchw(x, self.packed(H), self.modes1, self.modes2, self.out_channels)
 
 
 class SpectralConv1d(nn.Module):
@@ -350,16 +349,16 @@ class SpectralConv3d(nn.Module):
             raise NotImplementedError("FiLM spectral conditioning is not on the MI355X path")
         B, C, D, H, W = x.shape
         ops.check_modes3d(D, H, W, self.modes1, self.modes2, self.modes3)
-        x4 = x.reshape(B, C, D * H, W)
         if x.dtype == torch.bfloat16:  # bf16 storage (C5), inference only
+            x4 = x.reshape(B, C, D * H, W)
             xb = ops.to_bf16(ops.nchw_to_nhwc(ops.to_f32(x4.contiguous())))
             y = ops.nhwc_to_nchw(ops.to_f32(self.run_bf16([ops.Src(xb)], D)))
             return ops.to_bf16(y).reshape(B, self.out_channels, D, H, W)
+        # fp32: the module's own NCDHW tensors go straight to the channels-first W passes
         if use_autograd(self):
-            y = ad.to_nchw(ad.spectral_conv3d(self, ad.to_nhwc(x4), D))
-        else:
-            y = ops.nhwc_to_nchw(self.run([ops.Src(ops.nchw_to_nhwc(x4))], D))
-        return y.reshape(B, self.out_channels, D, H, W)
+            return ad.spectral_conv3d_nchw(self, x)
+        return ops.spectral_conv3d_nchw(x, self.packed(D, H), self.modes1, self.modes2, self.modes3,
+                                        self.out_channels)
 
 
 def get_spectral_conv_with_right_spatial_dim(spatial_dim, **kwargs):

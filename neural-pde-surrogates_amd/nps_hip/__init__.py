@@ -162,6 +162,15 @@ _SIGS = {
     "nps_spectral_conv3d_workspace": (_sz, [_i] * 9),
     "nps_spectral_conv3d_fwd": (_i, [_vp] * 7 + [_i] * 11 + [_vp]),
     "nps_spectral_conv3d_bwd": (_i, [_vp] * 12 + [_i] * 9 + [_vp]),
+    # channels-first (NCHW / NCDHW) W passes and composites; batch strides are longs (elements, 0 = dense)
+    "nps_spectral_dft_w_nchw": (_i, [_vp, _l, _i, _i, _i, _i, _i, _vp, _vp]),
+    "nps_spectral_idft_w_nchw": (_i, [_vp, _vp, _l, _i, _i, _i, _i, _i, _i, _i, _vp]),
+    "nps_spectral_idft_w_bwd_nchw": (_i, [_vp, _l, _vp, _i, _i, _i, _i, _i, _vp]),
+    "nps_spectral_dft_w_bwd_nchw": (_i, [_vp, _vp, _l, _i, _i, _i, _i, _i, _vp]),
+    "nps_spectral_conv2d_fwd_nchw": (_i, [_vp, _l, _vp, _vp, _vp, _l, _vp] + [_i] * 9 + [_vp]),
+    "nps_spectral_conv2d_bwd_nchw": (_i, [_vp, _l, _vp, _vp, _vp, _l, _vp, _l, _vp, _vp, _vp] + [_i] * 7 + [_vp]),
+    "nps_spectral_conv3d_fwd_nchw": (_i, [_vp, _l] + [_vp] * 5 + [_l, _vp] + [_i] * 11 + [_vp]),
+    "nps_spectral_conv3d_bwd_nchw": (_i, [_vp, _l] + [_vp] * 5 + [_l, _vp, _l] + [_vp] * 5 + [_i] * 9 + [_vp]),
     # bf16 storage (C5)
     "nps_spectral_dft_w_bf16": (_i, [ctypes.POINTER(Src), _i, _i, _i, _i, _i, _i, _vp, _vp]),
     "nps_spectral_mix_bf16": (_i, [_vp, _vp, _vp, _i, _i, _i, _i, _i, _vp]),

@@ -701,6 +701,121 @@ def spectral_conv3d(module, x, D):
                                   module.packed(D, H))
 
 
+class SpectralConv2dNchwFn(torch.autograd.Function):
+    """SpectralConv2dFn on the module's own NCHW tensors: x (B, Cin, H, W) -> (B, Cout, H, W), gy read and dx
+    written channels-first (no transposes); the saved tensors are the same X2 and wpack."""
+
+    @staticmethod
+    def forward(ctx, meta, x, w1, w2, wpack):
+        m1, m2, Cout = meta
+        x, x_bs = ops.channels_first(x)
+        B, Cin, H, W = x.shape
+        y = torch.empty((B, Cout, H, W), dtype=torch.float32, device=x.device)
+        X2 = ops.spectral_conv2d_nchw_stages(x, x_bs, wpack, m1, m2, Cout, y, 0)
+        ctx.meta, ctx.shape = meta, (B, H, W, Cin)
+        ctx.save_for_backward(X2, wpack)
+        return y
+
+    @staticmethod
+    def backward(ctx, gy):
+        m1, m2, Cout = ctx.meta
+        B, H, W, Cin = ctx.shape
+        X2, wpack = ctx.saved_tensors
+        R = X2.shape[1]
+        gy, gy_bs = ops.channels_first(gy)
+        dev = gy.device
+        s = stream_ptr()
+        gZ = torch.empty((B, H, m2, Cout), dtype=torch.complex64, device=dev)
+        gY = torch.empty((B, R, m2, Cout), dtype=torch.complex64, device=dev)
+        gX2 = torch.empty((B, R, m2, Cin), dtype=torch.complex64, device=dev)
+        gwp = torch.empty((R, m2, Cin, Cout), dtype=torch.complex64, device=dev)
+        check(lib.nps_spectral_idft_w_bwd_nchw(ptr(gy), gy_bs, ptr(gZ), B, H, W, m2, Cout, s),
+              "spectral_idft_w_bwd_nchw")
+        check(lib.nps_spectral_dft_h(ptr(gZ), ptr(gY), B, H, m1, m2, Cout, s), "spectral_dft_h (bwd)")
+        check(lib.nps_spectral_mix_bwd(ptr(X2), ptr(wpack), ptr(gY), ptr(gX2), ptr(gwp), B, R, m2, Cin, Cout, s),
+              "spectral_mix_bwd")
+        dx = dw1 = dw2 = None
+        if ctx.needs_input_grad[1]:
+            gX1 = torch.empty((B, H, m2, Cin), dtype=torch.complex64, device=dev)
+            check(lib.nps_spectral_idft_h(ptr(gX2), ptr(gX1), B, H, m1, m2, Cin, s), "spectral_idft_h (bwd)")
+            dx = torch.empty((B, Cin, H, W), dtype=torch.float32, device=dev)
+            check(lib.nps_spectral_dft_w_bwd_nchw(ptr(gX1), ptr(dx), 0, B, H, W, m2, Cin, s),
+                  "spectral_dft_w_bwd_nchw")
+        if ctx.needs_input_grad[2] or ctx.needs_input_grad[3]:
+            dw1 = torch.empty((Cin, Cout, m1, m2), dtype=torch.complex64, device=dev)
+            dw2 = torch.empty((Cin, Cout, m1, m2), dtype=torch.complex64, device=dev)
+            check(lib.nps_spectral_unpack_grad(ptr(gwp), ptr(dw1), ptr(dw2), Cin, Cout, H, m1, m2, s),
+                  "spectral_unpack_grad")
+        return None, dx, dw1, dw2, None
+
+
+def spectral_conv2d_nchw(module, x):
+    H = x.shape[2]
+    return SpectralConv2dNchwFn.apply((module.modes1, module.modes2, module.out_channels), x, module.weights1,
+                                      module.weights2, module.packed(H))
+
+
+class SpectralConv3dNchwFn(torch.autograd.Function):
+    """SpectralConv3dFn on the module's own NCDHW tensors: x (B, Cin, D, H, W) -> (B, Cout, D, H, W), gy read and
+    dx written channels-first; the saved tensors are the same X3 and wpack."""
+
+    @staticmethod
+    def forward(ctx, meta, x, w1, w2, w3, w4, wpack):
+        m1, m2, m3, Cout = meta
+        x, x_bs = ops.channels_first(x)
+        B, Cin, D, H, W = x.shape
+        y = torch.empty((B, Cout, D, H, W), dtype=torch.float32, device=x.device)
+        X3 = ops.spectral_conv3d_nchw_stages(x, x_bs, wpack, m1, m2, m3, Cout, y, 0)
+        ctx.meta, ctx.shape = meta, (B, D, H, W, Cin)
+        ctx.save_for_backward(X3, wpack)
+        return y
+
+    @staticmethod
+    def backward(ctx, gy):
+        m1, m2, m3, Cout = ctx.meta
+        B, D, H, W, Cin = ctx.shape
+        X3, wpack = ctx.saved_tensors
+        R1, R2 = min(D, 2 * m1), min(H, 2 * m2)
+        gy, gy_bs = ops.channels_first(gy)
+        dev = gy.device
+        c64 = torch.complex64
+        s = stream_ptr()
+        gZ2 = torch.empty((B, D * H, m3, Cout), dtype=c64, device=dev)
+        gZ1 = torch.empty((B * D, R2, m3, Cout), dtype=c64, device=dev)
+        gY = torch.empty((B, R1, R2 * m3, Cout), dtype=c64, device=dev)
+        gX3 = torch.empty((B, R1, R2 * m3, Cin), dtype=c64, device=dev)
+        gwp = torch.empty((R1, R2, m3, Cin, Cout), dtype=c64, device=dev)
+        check(lib.nps_spectral_idft_w_bwd_nchw(ptr(gy), gy_bs, ptr(gZ2), B, D * H, W, m3, Cout, s),
+              "spectral3d idft_w_bwd_nchw")
+        check(lib.nps_spectral_dft_h(ptr(gZ2), ptr(gZ1), B * D, H, m2, m3, Cout, s), "spectral3d dft_h (H, bwd)")
+        check(lib.nps_spectral_dft_h(ptr(gZ1), ptr(gY), B, D, m1, R2 * m3, Cout, s), "spectral3d dft_h (D, bwd)")
+        check(lib.nps_spectral_mix_bwd(ptr(X3), ptr(wpack), ptr(gY), ptr(gX3), ptr(gwp), B, R1, R2 * m3, Cin, Cout,
+                                       s), "spectral3d mix_bwd")
+        dx = None
+        gws = [None] * 4
+        if ctx.needs_input_grad[1]:
+            gX2 = torch.empty((B, D, R2 * m3, Cin), dtype=c64, device=dev)
+            gX1 = torch.empty((B * D, H, m3, Cin), dtype=c64, device=dev)
+            check(lib.nps_spectral_idft_h(ptr(gX3), ptr(gX2), B, D, m1, R2 * m3, Cin, s), "spectral3d idft_h (D, bwd)")
+            check(lib.nps_spectral_idft_h(ptr(gX2), ptr(gX1), B * D, H, m2, m3, Cin, s), "spectral3d idft_h (H, bwd)")
+            dx = torch.empty((B, Cin, D, H, W), dtype=torch.float32, device=dev)
+            check(lib.nps_spectral_dft_w_bwd_nchw(ptr(gX1), ptr(dx), 0, B, D * H, W, m3, Cin, s),
+                  "spectral3d dft_w_bwd_nchw")
+        if any(ctx.needs_input_grad[2:6]):
+            gws = [torch.empty((Cin, Cout, m1, m2, m3), dtype=c64, device=dev) for _ in range(4)]
+            check(lib.nps_spectral3d_unpack_grad(ptr(gwp), *[ptr(g) for g in gws], Cin, Cout, D, H, m1, m2, m3, s),
+                  "spectral3d_unpack_grad")
+        return (None, dx, *gws, None)
+
+
+def spectral_conv3d_nchw(module, x):
+    """x: (B, Cin, D, H, W) -> (B, Cout, D, H, W)."""
+    D, H = x.shape[2], x.shape[3]
+    return SpectralConv3dNchwFn.apply((module.modes1, module.modes2, module.modes3, module.out_channels), x,
+                                      module.weights1, module.weights2, module.weights3, module.weights4,
+                                      module.packed(D, H))
+
+
 # ------------------------------------------------------------------------- decoder / wrapper / loss
 class TimeConvDecodeFn(torch.autograd.Function):
     """TimeConvDense conv1d chain + add_delta('per_step') + tanh + spatial-cond mask

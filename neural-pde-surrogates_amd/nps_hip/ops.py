@@ -877,6 +877,105 @@ def spectral_conv3d(srcs: Sequence[Src], D: int, wpack: torch.Tensor, m1: int, m
     return out
 
 
+# ------------------------------------------------- channels-first spectral convs -----
+def channels_first(x: torch.Tensor):
+    """(x, batch stride in elements) for the channels-first kernels: an fp32 ROCm tensor whose inner (C, *spatial)
+    block is contiguous is passed as it lies (a channel slice of a larger tensor keeps its batch stride); anything
+    else is made contiguous first."""
+    ptr(x)  # no CPU path
+    if x.dtype != torch.float32:
+        raise TypeError(f"channels-first spectral convs take fp32 tensors, got {x.dtype}")
+    inner = x[0].numel()
+    if not (x[0].is_contiguous() and (x.shape[0] == 1 or x.stride(0) >= inner)):
+        x = x.contiguous()
+    return x, (0 if x.shape[0] == 1 else x.stride(0))
+
+
+def _out_channels_first(out, shape, like):
+    if out is None:
+        return torch.empty(shape, dtype=torch.float32, device=like.device), 0, False
+    o, obs = channels_first(out)
+    if o is not out or tuple(out.shape) != tuple(shape):
+        raise ValueError("out must be an fp32 channels-first tensor of the result's shape with a contiguous "
+                         "(C, *spatial) block")
+    return out, obs, True
+
+
+def spectral_mid2d(X1, wpack, B, H, m1, m2, Cin, Cout):
+    """The layout-independent middle of SpectralConv2d: X1 -> (X2 kept for the backward, Z)."""
+    R = min(H, 2 * m1)
+    dev = X1.device
+    X2 = torch.empty((B, R, m2, Cin), dtype=torch.complex64, device=dev)
+    Y = torch.empty((B, R, m2, Cout), dtype=torch.complex64, device=dev)
+    Z = torch.empty((B, H, m2, Cout), dtype=torch.complex64, device=dev)
+    s = stream_ptr()
+    check(lib.nps_spectral_dft_h(ptr(X1), ptr(X2), B, H, m1, m2, Cin, s), "spectral_dft_h")
+    check(lib.nps_spectral_mix(ptr(X2), ptr(wpack), ptr(Y), B, R, m2, Cin, Cout, s), "spectral_mix")
+    check(lib.nps_spectral_idft_h(ptr(Y), ptr(Z), B, H, m1, m2, Cout, s), "spectral_idft_h")
+    return X2, Z
+
+
+def spectral_conv2d_nchw_stages(x, x_bs, wpack, m1, m2, Cout, out, out_bs, accumulate=False, act=0):
+    """SpectralConv2d forward chain reading x and writing out channels-first.  Returns X2 (kept for the backward)."""
+    B, Cin, H, W = x.shape
+    if not (m1 <= H and m2 <= W // 2 + 1):
+        raise AssertionError("modes should be at most the spatial dim (// 2 + 1 for the last spatial dimension)")
+    X1 = torch.empty((B, H, m2, Cin), dtype=torch.complex64, device=x.device)
+    s = stream_ptr()
+    check(lib.nps_spectral_dft_w_nchw(ptr(x), x_bs, B, H, W, Cin, m2, ptr(X1), s), "spectral_dft_w_nchw")
+    X2, Z = spectral_mid2d(X1, wpack, B, H, m1, m2, Cin, Cout)
+    check(lib.nps_spectral_idft_w_nchw(ptr(Z), ptr(out), out_bs, B, H, W, m2, Cout, 1 if accumulate else 0, act, s),
+          "spectral_idft_w_nchw")
+    return X2
+
+
+def spectral_conv2d_nchw(x: torch.Tensor, wpack: torch.Tensor, m1: int, m2: int, Cout: int,
+                         out: Optional[torch.Tensor] = None, accumulate=False, act=0):
+    """y = irfft2(P(rfft2(x))) on the retained modes (proc_fno.py:257-288), NCHW in / out with no transpose: x
+    (B, Cin, H, W) -> (B, Cout, H, W); out (= or +=, then act) may be a channel slice of a larger tensor."""
+    x, x_bs = channels_first(x)
+    B, _, H, W = x.shape
+    out, out_bs, given = _out_channels_first(out, (B, Cout, H, W), x)
+    spectral_conv2d_nchw_stages(x, x_bs, wpack, m1, m2, Cout, out, out_bs, accumulate and given, act)
+    return out
+
+
+def spectral_conv3d_nchw_stages(x, x_bs, wpack, m1, m2, m3, Cout, out, out_bs, accumulate=False, act=0):
+    """SpectralConv3d forward chain on NCDHW x / out (viewed as (B, C, D*H, W)).  Returns X3 (kept for the backward)."""
+    B, Cin, D, H, W = x.shape
+    check_modes3d(D, H, W, m1, m2, m3)
+    R1, R2 = min(D, 2 * m1), min(H, 2 * m2)
+    dev = x.device
+    c64 = torch.complex64
+    X1 = torch.empty((B, D * H, m3, Cin), dtype=c64, device=dev)
+    X2 = torch.empty((B * D, R2, m3, Cin), dtype=c64, device=dev)
+    X3 = torch.empty((B, R1, R2 * m3, Cin), dtype=c64, device=dev)
+    Y = torch.empty((B, R1, R2 * m3, Cout), dtype=c64, device=dev)
+    Z1 = torch.empty((B, D, R2 * m3, Cout), dtype=c64, device=dev)
+    Z2 = torch.empty((B * D, H, m3, Cout), dtype=c64, device=dev)
+    s = stream_ptr()
+    check(lib.nps_spectral_dft_w_nchw(ptr(x), x_bs, B, D * H, W, Cin, m3, ptr(X1), s), "spectral3d dft_w_nchw")
+    check(lib.nps_spectral_dft_h(ptr(X1), ptr(X2), B * D, H, m2, m3, Cin, s), "spectral3d dft_h (H)")
+    check(lib.nps_spectral_dft_h(ptr(X2), ptr(X3), B, D, m1, R2 * m3, Cin, s), "spectral3d dft_h (D)")
+    check(lib.nps_spectral_mix(ptr(X3), ptr(wpack), ptr(Y), B, R1, R2 * m3, Cin, Cout, s), "spectral3d mix")
+    check(lib.nps_spectral_idft_h(ptr(Y), ptr(Z1), B, D, m1, R2 * m3, Cout, s), "spectral3d idft_h (D)")
+    check(lib.nps_spectral_idft_h(ptr(Z1), ptr(Z2), B * D, H, m2, m3, Cout, s), "spectral3d idft_h (H)")
+    check(lib.nps_spectral_idft_w_nchw(ptr(Z2), ptr(out), out_bs, B, D * H, W, m3, Cout, 1 if accumulate else 0, act,
+                                       s), "spectral3d idft_w_nchw")
+    return X3
+
+
+def spectral_conv3d_nchw(x: torch.Tensor, wpack: torch.Tensor, m1: int, m2: int, m3: int, Cout: int,
+                         out: Optional[torch.Tensor] = None, accumulate=False, act=0):
+    """y = irfftn(P(rfftn(x))) on the 4 retained corners (proc_fno.py:334-376), NCDHW in / out with no transpose:
+    x (B, Cin, D, H, W) -> (B, Cout, D, H, W)."""
+    x, x_bs = channels_first(x)
+    B, _, D, H, W = x.shape
+    out, out_bs, given = _out_channels_first(out, (B, Cout, D, H, W), x)
+    spectral_conv3d_nchw_stages(x, x_bs, wpack, m1, m2, m3, Cout, out, out_bs, accumulate and given, act)
+    return out
+
+
 # ------------------------------------------------------------------ bf16 storage (C5) -----
 def _c_src_bf16(srcs: Sequence[Src]):
     arr = (_CSrc * 3)()
