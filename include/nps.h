@@ -335,7 +335,11 @@ int nps_spectral_dft_w_bf16(const nps_src_t* src, int nsrc, int B, int H, int W,
  * (nps_f32_to_bf16 of the fp32 packing) */
 int nps_spectral_mix_bf16(const float* X2, const void* wpack, float* Y, int B, int R, int m2, int Cin, int Cout,
                           void* stream);
-/* out / addend bf16 [B][H][W][Cout]; out (= or +=) act(c2r(Z)/(H W) + addend) */
+/* out / addend bf16 [B][H][W][Cout]; out (= or +=) act(c2r(Z)/(H W) + addend).  The bins are summed 16 at a time and
+ * the running sum lives in `out` between chunks: for m2 <= 16 (C5: m3 = 12) the fp32 sum is rounded to bf16 once, at
+ * the store; for m2 > 16 the partial sums are also rounded to bf16, once per extra chunk (the partial over the first
+ * 16 j bins, j = 1, 2, ..., adds up to 2^-8 of its magnitude to the error of the result;
+ * tests/test_gpu_bf16_stages.py). */
 int nps_spectral_idft_w_bf16(const float* Z, void* out, int B, int H, int W, int m2, int Cout, int accumulate,
                              const void* addend, int act, void* stream);
 /* elementwise conversion (bf16 round-to-nearest-even) */
