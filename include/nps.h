@@ -567,6 +567,26 @@ int nps_frame_pack3d(const nps_conv3d_t* a, void* out, int Cpad, void* stream);
  * fp64 (sum, sum of squares) of the frame's values (uncovered positions count as 0) to stats[B][G][2] */
 int nps_gn_stats3d(const nps_conv3d_t* a, int G, double* stats, void* stream);
 
+/* ---- U-Net self-attention (proc_unet_modern.py:292-317), never materialising the N x N scores ----
+ * Layouts, exactly as the qkv projection writes them (no q / k / v split copies):
+ *   qkv, dqkv [B][N][heads][3*dk]  (per head [q | k | v], dk floats each)
+ *   out, dout [B][N][heads*dk]
+ *   lse       [B][heads][N]
+ * The reference's softmax runs over the QUERY index i for each key j (softmax(dim=1)):
+ *   P[i][j] = exp(scale q_i.k_j - lse[j]),  lse[j] = log sum_i exp(scale q_i.k_j),  out_i = sum_j P[i][j] v_j.
+ * nps_attn_colstats computes lse (per key tile, an online max / sum over query tiles); nps_attn_fwd then needs
+ * no running rescale.  nps_attn_bwd writes every element of dqkv (dV_j = sum_i P dO_i, delta_j = dV_j.v_j,
+ * dS = P (dO_i.v_j - delta_j), dK_j = scale sum_i dS q_i, dQ_i = scale sum_j dS k_j; P recomputed from lse) and
+ * uses ws[nps_attn_bwd_ws_floats(...)] floats of scratch (delta).  Exact-fp32 MFMA, fp32 expf.
+ * dk % 4 == 0, 4 <= dk <= 256; heads, B >= 1 (<= 65535); N >= 1; 16-byte aligned tensors.  Anything else
+ * returns < 0 with nps_last_error set. */
+int nps_attn_colstats(const float* qkv, float* lse, int B, int N, int heads, int dk, float scale, void* stream);
+int nps_attn_fwd(const float* qkv, const float* lse, float* out, int B, int N, int heads, int dk, float scale,
+                 void* stream);
+size_t nps_attn_bwd_ws_floats(int B, int N, int heads, int dk);
+int nps_attn_bwd(const float* qkv, const float* lse, const float* dout, float* dqkv, float* ws, int B, int N,
+                 int heads, int dk, float scale, void* stream);
+
 const char* nps_last_error(void);
 const char* nps_version(void);
 

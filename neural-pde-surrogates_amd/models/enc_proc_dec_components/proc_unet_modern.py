@@ -118,7 +118,7 @@ class UNetModern(nn.Module):
                 srcs = [ops.Src(h), ops.Src(s, *crop_offsets(s.shape[1:3], (H, W)))]
                 if v is not None:
                     srcs.append(ops.Src(v, *crop_offsets(v.shape[1:3], (H, W))))
-                h = m.res.run(srcs, (H, W))
+                h = _attn(m, m.res.run(srcs, (H, W)))
         # final: conv(act(norm(h))) then crop_Nd to the input size, as one launch
         H, W = h.shape[1:3]
         gn = None
@@ -160,14 +160,13 @@ class UNetModern(nn.Module):
             if isinstance(m, Upsample):
                 h = ad.conv_transpose2d(m.conv, h)
             else:
-                _check_no_attn(m)
                 s = feats.pop()
                 v = vbs.pop()
                 H, W = h.shape[1:3]
                 srcs = [ops.Src(h), ops.Src(s, *crop_offsets(s.shape[1:3], (H, W)))]
                 if v is not None:
                     srcs.append(ops.Src(v, *crop_offsets(v.shape[1:3], (H, W))))
-                h = m.res.run_ad(srcs, (H, W))
+                h = _attn_ad(m, m.res.run_ad(srcs, (H, W)))
         H, W = h.shape[1:3]
         norm = self.norm if isinstance(self.norm, nn.GroupNorm) else None
         y = ad.conv2d(self.final, ad.frame([ops.Src(h)], (H, W), norm, activation_code(self.activation)))
@@ -410,8 +409,42 @@ class ResidualBlock(nn.Module):
         return ops.nhwc_to_nchw(self.run([ops.Src(x)], x.shape[1:3]))
 
 
+_GEO_1X1 = (1, 1, 1, 1, (0, 0), (0, 0), 0)  # Conv2d.geometry() of a 1x1 conv
+
+
+def _conv_weight(mod):
+    """The weight of an nn.Linear / kernel-1 nn.Conv1d / 1x1 Conv2d as a (out, in, 1, 1) conv weight.  A Linear or
+    Conv1d weight is viewed, not copied (gradients reach the parameter through the view); the fresh view shares
+    one packing cache kept on the module, so ops.cached_pack packs it once per parameter version."""
+    w = mod.weight
+    if w.dim() == 4:
+        return w
+    if w.dim() == 3 and w.shape[2] != 1:
+        raise NotImplementedError("attention shortcut: kernel-1 conv only")
+    w4 = w.view(w.shape[0], w.shape[1], 1, 1)
+    w4._nps_packs = mod.__dict__.setdefault("_nps_packs_1x1", {})
+    return w4
+
+
+def _run_1x1(mod, x, **kw):
+    """mod (Linear / kernel-1 conv) applied per position of the NHWC map x on the fused 1x1 conv path."""
+    w4 = _conv_weight(mod)
+    pk = ops.cached_pack(w4, ("conv", 1, 1), lambda w: ops.pack_conv_weight(w, 1, 1))
+    return ops.conv2d([ops.Src(x)], x.shape[1:3], pk, mod.bias, w4.shape[0], 1, 1, **kw)
+
+
+def _run_1x1_ad(mod, x):
+    return ad.Conv2dFn.apply(_GEO_1X1, x, _conv_weight(mod), mod.bias)
+
+
 class AttentionBlock(nn.Module):
-    """proc_unet_modern.py:253-317 — parameters only (is_attn / mid_attn are False in every cfg)."""
+    """proc_unet_modern.py:253-317.  Tokens are the flattened positions of the map; `norm` exists as parameters
+    and is never applied (:292-317 do not call it), so it stays in the state_dict and receives no gradient.  The
+    softmax runs over the QUERY index for each key (:304, dim=1).  On NHWC maps the token-major [B, N, C] view is
+    the map itself: `projection` and `output` run as 1x1 convs, the attention itself on nps_attn_* (no N x N
+    scores), and `output`'s epilogue adds the shortcut.  The reference's forward only runs with one head and the
+    identity shortcut (`res.view` at :308 needs a contiguous einsum result; :313 hands the shortcut conv the
+    token-major view); more heads and the kernel-1 shortcut conv are computed here as those lines intend."""
 
     def __init__(self, in_channels: int, out_channels: int = None, n_heads: int = 1, d_k=None, n_groups: int = 1,
                  num_spatial_dims: int = 1):
@@ -430,13 +463,47 @@ class AttentionBlock(nn.Module):
         else:
             self.shortcut = nn.Identity()
 
-    def forward(self, x):
-        raise NotImplementedError("U-Net attention is not on the MI355X path (is_attn=False in all cfgs)")
+    def run(self, x):
+        """NHWC inference forward.  x is only read (its producer's other consumers still use it); the result is a
+        new tensor carrying its own GroupNorm(1) moments (or none, when the launch cannot take them: the next
+        norm1 then runs a statistics pass) — never x's."""
+        B, H, W, _ = x.shape
+        qkv = _run_1x1(self.projection, x)
+        o, _ = ops.attention(qkv.view(B, H * W, -1), self.n_heads, self.d_k, self.scale)
+        sc = x if isinstance(self.shortcut, nn.Identity) else _run_1x1(self.shortcut, x)
+        st = ops.new_stats(B, x)
+        y = _run_1x1(self.output, o.view(B, H, W, -1), addends=[sc], out_stats=st)
+        return ops.attach_stats(y, st)
+
+    def run_ad(self, x):
+        """Differentiable NHWC forward (training): the same launches unfused, gradients through Conv2dFn (the
+        projections) and nps_attn_bwd."""
+        B, H, W, _ = x.shape
+        qkv = _run_1x1_ad(self.projection, x)
+        o = ad.attention(qkv.view(B, H * W, -1), self.n_heads, self.d_k, self.scale)
+        y = _run_1x1_ad(self.output, o.view(B, H, W, -1))
+        sc = x if isinstance(self.shortcut, nn.Identity) else _run_1x1_ad(self.shortcut, x)
+        return ad.add_at(sc, y)
+
+    def forward(self, x: torch.Tensor):
+        if x.dim() != 4:
+            raise NotImplementedError("U-Net attention: 2-D maps only on the MI355X path")
+        if use_autograd(self):
+            return ad.to_nchw(self.run_ad(ad.to_nhwc(x)))
+        return ops.nhwc_to_nchw(self.run(ops.nchw_to_nhwc(x)))
 
 
 def _check_no_attn(m):
     if not isinstance(m.attn, nn.Identity):
-        raise NotImplementedError("U-Net attention is not on the MI355X path (is_attn=False in all cfgs)")
+        raise NotImplementedError("3-D U-Net attention is not on the MI355X path")
+
+
+def _attn(m, h):
+    return h if isinstance(m.attn, nn.Identity) else m.attn.run(h)
+
+
+def _attn_ad(m, h):
+    return h if isinstance(m.attn, nn.Identity) else m.attn.run_ad(h)
 
 
 class DownBlock(nn.Module):
@@ -450,14 +517,12 @@ class DownBlock(nn.Module):
         self.attn = AttentionBlock(out_channels, num_spatial_dims=num_spatial_dims) if has_attn else nn.Identity()
 
     def run(self, x, vb):
-        _check_no_attn(self)
         srcs = [ops.Src(x)] + ([ops.Src(vb)] if vb is not None else [])
-        return self.res.run(srcs, x.shape[1:3])
+        return _attn(self, self.res.run(srcs, x.shape[1:3]))
 
     def run_ad(self, x, vb):
-        _check_no_attn(self)
         srcs = [ops.Src(x)] + ([ops.Src(vb)] if vb is not None else [])
-        return self.res.run_ad(srcs, x.shape[1:3])
+        return _attn_ad(self, self.res.run_ad(srcs, x.shape[1:3]))
 
     def run3d(self, x, vb):
         _check_no_attn(self)
@@ -486,14 +551,14 @@ class UpBlock(nn.Module):
         self.attn = AttentionBlock(out_channels, num_spatial_dims=num_spatial_dims) if has_attn else nn.Identity()
 
     def forward(self, x: torch.Tensor):
-        _check_no_attn(self)
         if self.res.num_spatial_dims == 3:
+            _check_no_attn(self)
             return self.res(x)
         if use_autograd(self):
             x = ad.to_nhwc(x)
-            return ad.to_nchw(self.res.run_ad([ops.Src(x)], x.shape[1:3]))
+            return ad.to_nchw(_attn_ad(self, self.res.run_ad([ops.Src(x)], x.shape[1:3])))
         x = ops.nchw_to_nhwc(x)
-        return ops.nhwc_to_nchw(self.res.run([ops.Src(x)], x.shape[1:3]))
+        return ops.nhwc_to_nchw(_attn(self, self.res.run([ops.Src(x)], x.shape[1:3])))
 
 
 class MiddleBlock(nn.Module):
@@ -509,15 +574,13 @@ class MiddleBlock(nn.Module):
                                   num_spatial_dims=num_spatial_dims, padding_kwargs=padding_kwargs)
 
     def run(self, x, vb):
-        _check_no_attn(self)
         srcs = [ops.Src(x)] + ([ops.Src(vb)] if vb is not None else [])
-        h = self.res1.run(srcs, x.shape[1:3])
+        h = _attn(self, self.res1.run(srcs, x.shape[1:3]))
         return self.res2.run([ops.Src(h)], h.shape[1:3])
 
     def run_ad(self, x, vb):
-        _check_no_attn(self)
         srcs = [ops.Src(x)] + ([ops.Src(vb)] if vb is not None else [])
-        h = self.res1.run_ad(srcs, x.shape[1:3])
+        h = _attn_ad(self, self.res1.run_ad(srcs, x.shape[1:3]))
         return self.res2.run_ad([ops.Src(h)], h.shape[1:3])
 
     def run3d(self, x, vb):

@@ -186,6 +186,11 @@ _SIGS = {
     "nps_conv3d_fwd": (_i, [ctypes.POINTER(Conv3dArgs), _vp]),
     "nps_gn_stats3d": (_i, [ctypes.POINTER(Conv3dArgs), _i, _vp, _vp]),
     "nps_frame_pack3d": (_i, [ctypes.POINTER(Conv3dArgs), _vp, _i, _vp]),
+    # U-Net self-attention (column softmax), flash-style
+    "nps_attn_colstats": (_i, [_vp, _vp, _i, _i, _i, _i, ctypes.c_float, _vp]),
+    "nps_attn_fwd": (_i, [_vp, _vp, _vp, _i, _i, _i, _i, ctypes.c_float, _vp]),
+    "nps_attn_bwd_ws_floats": (_sz, [_i, _i, _i, _i]),
+    "nps_attn_bwd": (_i, [_vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, ctypes.c_float, _vp]),
     "nps_last_error": (ctypes.c_char_p, []),
     "nps_version": (ctypes.c_char_p, []),
 }

@@ -945,3 +945,28 @@ class MseSumFn(torch.autograd.Function):
 
 def mse_sum(pred, labels):
     return MseSumFn.apply(pred, labels)
+
+
+# ------------------------------------------------------------------------- U-Net self-attention
+class AttentionFn(torch.autograd.Function):
+    """proc_unet_modern.py:300-308 (column softmax) on qkv (B, N, heads * 3 * dk); saves qkv and the column
+    log-sum-exp, and the backward recomputes the weights from them (nps_attn_bwd)."""
+
+    @staticmethod
+    def forward(ctx, meta, qkv):
+        heads, dk, scale = meta
+        qkv = _c(qkv)
+        out, lse = ops.attention(qkv, heads, dk, scale)
+        ctx.meta = meta
+        ctx.save_for_backward(qkv, lse)
+        return out
+
+    @staticmethod
+    def backward(ctx, gout):
+        heads, dk, scale = ctx.meta
+        qkv, lse = ctx.saved_tensors
+        return None, ops.attention_bwd(qkv, lse, _c(gout), heads, dk, scale)
+
+
+def attention(qkv: torch.Tensor, heads: int, dk: int, scale: float) -> torch.Tensor:
+    return AttentionFn.apply((int(heads), int(dk), float(scale)), qkv)

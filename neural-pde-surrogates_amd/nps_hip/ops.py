@@ -1309,3 +1309,39 @@ def sq_err_sum(a: torch.Tensor, b: torch.Tensor) -> torch.Tensor:
     out = torch.zeros(1, dtype=torch.float64, device=a.device)
     check(lib.nps_sq_err_sum(ptr(a), ptr(b), a.numel(), ptr(out), stream_ptr()), "sq_err_sum")
     return out[0]
+
+
+# -------------------------------------------------------------- U-Net self-attention ----
+def _attn_check(qkv: torch.Tensor, heads: int, dk: int):
+    if not qkv.is_cuda:
+        raise RuntimeError("nps_hip ops run on the MI355X only: tensor is on " + str(qkv.device))
+    if qkv.dtype != torch.float32 or not qkv.is_contiguous() or qkv.dim() != 3 or qkv.shape[2] != heads * 3 * dk:
+        raise RuntimeError(f"attention: qkv must be contiguous fp32 (B, N, heads * 3 * dk), got {qkv.dtype} "
+                           f"{tuple(qkv.shape)} for heads={heads}, dk={dk}")
+
+
+def attention(qkv: torch.Tensor, heads: int, dk: int, scale: float):
+    """proc_unet_modern.py:300-308 on the projection's output qkv (B, N, heads * 3 * dk), per head [q | k | v]:
+    softmax over the QUERY index for each key (dim=1), never materialising the scores.  Returns
+    (out (B, N, heads * dk), lse (B, heads, N)) — lse is what attention_bwd recomputes the weights from."""
+    _attn_check(qkv, heads, dk)
+    B, N = qkv.shape[0], qkv.shape[1]
+    lse = torch.empty((B, heads, N), dtype=torch.float32, device=qkv.device)
+    out = torch.empty((B, N, heads * dk), dtype=torch.float32, device=qkv.device)
+    check(lib.nps_attn_colstats(ptr(qkv), ptr(lse), B, N, heads, dk, float(scale), stream_ptr()), "attn_colstats")
+    check(lib.nps_attn_fwd(ptr(qkv), ptr(lse), ptr(out), B, N, heads, dk, float(scale), stream_ptr()), "attn_fwd")
+    return out, lse
+
+
+def attention_bwd(qkv: torch.Tensor, lse: torch.Tensor, dout: torch.Tensor, heads: int, dk: int, scale: float):
+    """Gradient of attention() with respect to qkv (same layout)."""
+    _attn_check(qkv, heads, dk)
+    B, N = qkv.shape[0], qkv.shape[1]
+    dout = dout.contiguous()
+    if dout.dtype != torch.float32 or tuple(dout.shape) != (B, N, heads * dk) or tuple(lse.shape) != (B, heads, N):
+        raise RuntimeError("attention_bwd: dout must be fp32 (B, N, heads * dk) and lse (B, heads, N)")
+    dqkv = torch.empty_like(qkv)
+    ws = torch.empty(lib.nps_attn_bwd_ws_floats(B, N, heads, dk), dtype=torch.float32, device=qkv.device)
+    check(lib.nps_attn_bwd(ptr(qkv), ptr(lse), ptr(dout), ptr(dqkv), ptr(ws), B, N, heads, dk, float(scale),
+                           stream_ptr()), "attn_bwd")
+    return dqkv
