@@ -841,9 +841,10 @@ __global__ __launch_bounds__(512) void conv1x1_x3_kernel(const nps_conv2d_t a) {
 // 1x1 with the weights staged in LDS: a wave covers ALL output channels (NCB 32-channel blocks) of its
 // 32 pixels, so a work-group of 4 waves (128 pixels) fetches its input once per CU instead of once per
 // co-block wave.  Per 32-channel stage the 4 waves copy the stage's weight fragments (2 chunks x NCB
-// blocks x 2 KB) into one of two LDS buffers (fetched one stage ahead into registers, compiler-managed
-// loads), one barrier per stage; B as in conv1x1_x3_kernel (per-lane 64-B runs in a D-deep register
-// ring, zero page outside the frame).  Epilogue: store_tile per 32-channel block.
+// blocks x 2 KB) into one of two LDS buffers by LDS-DMA (one stage ahead, no staging registers), one
+// barrier per stage; B as in conv1x1_x3_kernel (per-lane 64-B runs in a D-deep register ring, zero page
+// outside the frame): D - 1 stages of input stay in flight, D - 2 of them across the stage barrier, which
+// waits for the DMA with a counted vmcnt.  Epilogue: store_tile per 32-channel block.
 // PRO: the frame prologue act(GroupNorm(frame)) (the U-Net's final GN(8) + GELU before its 1x1 conv,
 // proc_unet_modern.py:191-196) applied to each loaded input element before the split, instead of a frame_pack
 // pass: per-channel affine (scale, shift) of this work-group's sample in an LDS table built at kernel start from the
@@ -884,64 +885,83 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2))) void c
         fy = a.circ ? nps::wrap_mod(ye - a.circ, a.Hin) : ye;
         fx = a.circ ? nps::wrap_mod(xe - a.circ, a.Win) : xe;
     }
-    const float* sp = nullptr;
-    int cur_src = -1, cbase = 0;
-    auto locate = [&](int sidx) {
+    // Every source's address of this lane's pixel, minus the source's first frame channel, whether the source covers
+    // the pixel, and the zero page's address, once: the stage loop only selects among them.  (Found per stage, the
+    // source's index arithmetic and one scalar load of the zero page's address per 16-byte piece, each with its
+    // wait, stood in front of every stage's first MFMA.)  Kept as one address, two differences and a mask: a
+    // select among three pointer variables makes the compiler index them in scratch memory.
+    static_assert(NPS_MAX_SRC == 3, "three frame sources");
+    typedef const __attribute__((address_space(1))) float* gfp;  // (global: an address built from integers loads flat)
+    unsigned long long pa0, pd1, pd2;
+    int okmask;
+    {
         const nps_src_t S0 = a.src[0], S1 = a.src[1], S2 = a.src[2];
-        const float* sptr = sidx == 0 ? S0.ptr : (sidx == 1 ? S1.ptr : S2.ptr);
-        const int sC = sidx == 0 ? S0.C : (sidx == 1 ? S1.C : S2.C);
-        const int sH = sidx == 0 ? S0.H : (sidx == 1 ? S1.H : S2.H);
-        const int sW = sidx == 0 ? S0.W : (sidx == 1 ? S1.W : S2.W);
-        const int yy = fy - (sidx == 0 ? S0.off_y : (sidx == 1 ? S1.off_y : S2.off_y));
-        const int xx = fx - (sidx == 0 ? S0.off_x : (sidx == 1 ? S1.off_x : S2.off_x));
-        const bool ok = pin && yy >= 0 && yy < sH && xx >= 0 && xx < sW;
-        sp = ok ? sptr + ((size_t)(b * sH + yy) * sW + xx) * sC : nullptr;
-    };
+        auto covers = [&](int sH, int sW, int oy, int ox, bool used) {
+            const int yy = fy - oy, xx = fx - ox;
+            return used && pin && yy >= 0 && yy < sH && xx >= 0 && xx < sW;
+        };
+        auto addr = [&](const float* sptr, int sC, int sH, int sW, int oy, int ox, int lo) {  // (used where covered)
+            return reinterpret_cast<unsigned long long>(sptr) +
+                   ((((long long)b * sH + (fy - oy)) * sW + (fx - ox)) * sC - lo) * 4;
+        };
+        const unsigned long long pa1 = addr(S1.ptr, S1.C, S1.H, S1.W, S1.off_y, S1.off_x, S0.C);
+        pa0 = addr(S0.ptr, S0.C, S0.H, S0.W, S0.off_y, S0.off_x, 0);
+        pd1 = pa1 - pa0;
+        pd2 = addr(S2.ptr, S2.C, S2.H, S2.W, S2.off_y, S2.off_x, S0.C + S1.C) - pa1;
+        okmask = (covers(S0.H, S0.W, S0.off_y, S0.off_x, true) ? 1 : 0) |
+                 (covers(S1.H, S1.W, S1.off_y, S1.off_x, a.nsrc > 1) ? 2 : 0) |
+                 (covers(S2.H, S2.W, S2.off_y, S2.off_x, a.nsrc > 2) ? 4 : 0);
+    }
+    const int clo1 = a.nsrc > 1 ? a.src[0].C : 0x7fffffff;              // first frame channel of source 1
+    const int clo2 = a.nsrc > 2 ? a.src[0].C + a.src[1].C : 0x7fffffff;  // ... of source 2
+    gfp zero16;
+    {
+        const unsigned long long z = reinterpret_cast<unsigned long long>(x3_zero16);
+        const unsigned zl = __builtin_amdgcn_readfirstlane((unsigned)z);
+        const unsigned zh = __builtin_amdgcn_readfirstlane((unsigned)(z >> 32));
+        zero16 = (gfp)(((unsigned long long)zh << 32) | zl);
+    }
     const int nstages = (a.Cin + 2 * CK - 1) / (2 * CK);
     const int last = nstages - 1;
     f32x4 raw[D][4];
-    auto issue = [&](int st, bool live, f32x4 (&r)[4]) {
-        const int c0 = st * 2 * CK + h * CK;
-        int sidx = 0, lo = 0, sb = 0;
-#pragma unroll
-        for (int si = 0; si < NPS_MAX_SRC; ++si) {
-            if (si < a.nsrc) {
-                const int hi = lo + a.src[si].C;
-                if (c0 >= lo && c0 < hi) {
-                    sidx = si;
-                    sb = lo;
-                }
-                lo = hi;
-            }
-        }
-        if (sidx != cur_src) {
-            locate(sidx);
-            cur_src = sidx;
-            cbase = sb;
-        }
+    auto issue = [&](int st, bool live, f32x4 (&r)[4]) __attribute__((always_inline)) {
+        const int c0 = st * 2 * CK + h * CK;  // (a 16-channel run lies in one source: x3_sources_aligned)
+        const int sidx = (c0 >= clo1 ? 1 : 0) + (c0 >= clo2 ? 1 : 0);
+        const gfp sp = (gfp)(pa0 + (sidx >= 1 ? pd1 : 0ull) + (sidx >= 2 ? pd2 : 0ull));
+        const bool cov = ((okmask >> sidx) & 1) != 0;
 #pragma unroll
         for (int q = 0; q < 4; ++q) {
             const bool chok = live && c0 + q * 4 < a.Cin;
-            const float* src = (chok && sp != nullptr) ? sp + (c0 - cbase + q * 4) : x3_zero16;
-            r[q] = *reinterpret_cast<const f32x4*>(src);
+            const gfp src = (chok && cov) ? sp + (c0 + q * 4) : zero16;
+            r[q] = *(const __attribute__((address_space(1))) f32x4*)src;
         }
     };
     // weight stage st: chunks 2st, 2st + 1, blocks [0, NCB) of each (the packed chunk holds packed_ncb blocks)
     const size_t gstride = (size_t)packed_ncb(a.Cout) * 2048;
     const char* wg = reinterpret_cast<const char*>(a.wpack) + (size_t)grp * NCB * 2048;
-    f32x4 wr[WPT];
-    auto wfetch = [&](int st) {
+    // global (L2) -> LDS buffer buf by LDS-DMA, no staging registers: the copy is lane-linear (thread t's piece i at
+    // byte (i * 256 + t) * 16 of the stage), so wave wv's instruction i writes [(i * 256 + wv * 64) * 16, + 1 KiB).
+    // The issuing wave's vmcnt wait in front of the next barrier covers it (wsync).
+    auto wdma = [&](int st, int buf) {
 #pragma unroll
         for (int i = 0; i < WPT; ++i) {
-            const int off = (i * 256 + (int)threadIdx.x) * 16;  // byte offset inside the stage
-            const int k = off / (NCB * 2048), rem = off - k * (NCB * 2048);
-            wr[i] = *reinterpret_cast<const f32x4*>(wg + (size_t)(2 * st + k) * gstride + rem);
+            // byte (i * 256 + t) * 16 of the stage lies in chunk k at rem (k by i alone: 4 KiB pieces, NCB even)
+            static_assert((NCB * 2048) % 4096 == 0, "a 256-thread piece lies in one chunk");
+            const int k = (i * 4096) / (NCB * 2048);
+            const int rem = i * 4096 - k * (NCB * 2048) + (int)threadIdx.x * 16;
+            __builtin_amdgcn_global_load_lds((const void*)(wg + (size_t)(2 * st + k) * gstride + rem),
+                                             (__attribute__((address_space(3))) void*)(wl + buf * WSTAGE +
+                                                                                       (i * 256 + wv * 64) * 16),
+                                             16, 0, 0);
         }
     };
-    auto wstore = [&](int buf) {
-#pragma unroll
-        for (int i = 0; i < WPT; ++i)
-            *reinterpret_cast<f32x4*>(wl + buf * WSTAGE + (i * 256 + (int)threadIdx.x) * 16) = wr[i];
+    // The DMA is issued in front of the stage's 4 input loads, so vmcnt(4 (D - 2)) retires it (and the input of the
+    // next stage) and leaves the newest D - 2 stages of input in flight across the barrier; a plain
+    // __syncthreads() would drain them, since it waits vmcnt(0) while an LDS-DMA is pending.
+    static_assert(D >= 3 && 4 * (D - 2) <= 15, "ring depth");
+    auto wsync = [&]() {
+        __builtin_amdgcn_s_waitcnt(0x0070 | (4 * (D - 2)));  // vmcnt(4 (D - 2)) lgkmcnt(0)
+        __builtin_amdgcn_s_barrier();
     };
     if ((int)threadIdx.x < NCB * 32)  // the epilogue's bias table (zero past Cout), behind the first barrier
         reinterpret_cast<float*>(wl + 2 * WSTAGE)[threadIdx.x] =
@@ -975,72 +995,116 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2))) void c
     for (int i = 0; i < NCB; ++i)
 #pragma unroll
         for (int r = 0; r < 16; ++r) acc[i][r] = 0.f;
+    wdma(0, 0);  // (in front of the input loads: wsync)
     static_for<D - 1>([&](auto jc) {
         constexpr int j = decltype(jc)::value;
         issue(min(j, last), j <= last, raw[j]);
     });
-    wfetch(0);
-    wstore(0);
-    wfetch(min(1, last));
-    __syncthreads();
+    __builtin_amdgcn_s_waitcnt(0x0070 | (4 * (D - 2)));  // the DMA and stage 0's input; lgkmcnt(0): the tables
+    __builtin_amdgcn_s_barrier();
     const int npad = (nstages + D - 1) / D * D;
-    for (int s0 = 0; s0 < npad; s0 += D) {
-        static_for<D>([&](auto jc) {
-            constexpr int j = decltype(jc)::value;
-            constexpr int jn = (j + D - 1) % D;
-            const int st = s0 + j;
-            // weights of stage st + 1 (fetched last stage) -> the other buffer (its readers passed the
-            // previous barrier); then fetch stage st + 2's
-            wstore((st + 1) & 1);
-            wfetch(min(st + 2, last));
-            issue(min(st + D - 1, last), st + D - 1 <= last, raw[jn]);
-            __builtin_amdgcn_sched_barrier(0);
-            const char* wb = wl + (st & 1) * WSTAGE + lane * 16;
+    // quad q (4 channels) of chunk k (16 channels: 8 per lane half) of a staged 32-channel run -> split fp16 (hi, lo)
+    auto splitQ = [&](int st, int k, int q, const f32x4 (&rw)[4], f16x4& hi, f16x4& lo) __attribute__((always_inline)) {
+        f32x4 v = rw[2 * k + q];
+        if constexpr (PRO) {  // channels st * 32 + h * 16 + 8 k + 4 q + [0, 4) of this lane's pixel
+            // (the padded iterations of the ring, st > last, read no table: their input must stay 0)
+            const int ncp = ((a.Cin + 2 * CK - 1) / (2 * CK)) * 2 * CK;
+            const bool live = pin && st <= last;
+            const int c = min(st, last) * 2 * CK + h * CK + 8 * k + 4 * q;
+            const f32x4 sc = *reinterpret_cast<const f32x4*>(gtab + c);
+            const f32x4 sh = *reinterpret_cast<const f32x4*>(gtab + ncp + c);
 #pragma unroll
-            for (int k = 0; k < 2; ++k) {
-                f16x4 h0, l0, h1, l1;
-                f32x4 v0 = raw[j][2 * k], v1 = raw[j][2 * k + 1];
-                if constexpr (PRO) {  // channels st * 32 + h * 16 + 8 k + [0, 8) of this lane's pixel
-                    // (the padded iterations of the ring, st > last, read no table: their input must stay 0)
-                    const int ncp = ((a.Cin + 2 * CK - 1) / (2 * CK)) * 2 * CK;
-                    const bool live = pin && st <= last;
-                    const int c = min(st, last) * 2 * CK + h * CK + 8 * k;
-                    const f32x4 s0 = *reinterpret_cast<const f32x4*>(gtab + c);
-                    const f32x4 s1 = *reinterpret_cast<const f32x4*>(gtab + c + 4);
-                    const f32x4 b0 = *reinterpret_cast<const f32x4*>(gtab + ncp + c);
-                    const f32x4 b1 = *reinterpret_cast<const f32x4*>(gtab + ncp + c + 4);
-#pragma unroll
-                    for (int e = 0; e < 4; ++e) {
-                        float y0 = fmaf(v0[e], s0[e], b0[e]), y1 = fmaf(v1[e], s1[e], b1[e]);
-                        if (a.pre_act == 1) {
-                            y0 = nps::gelu_fast(y0);
-                            y1 = nps::gelu_fast(y1);
+            for (int e = 0; e < 4; ++e) {
+                float y = fmaf(v[e], sc[e], sh[e]);
+                if (a.pre_act == 1) y = nps::gelu_fast(y);
+                v[e] = live ? y : 0.f;  // (outside the frame: the conv's zero padding)
+            }
+        }
+        if (scaled) v *= xs;
+        split4(v, hi, lo);
+    };
+    auto cat8 = [](const f16x4 u, const f16x4 w) { return f16x8{u[0], u[1], u[2], u[3], w[0], w[1], w[2], w[3]}; };
+    // FULL: all NCB blocks of the group hold output channels (the launches with (NCB - 1) * 32 < Cout <= NCB * 32 and
+    // every full group of a wider one).  A stage is then a straight run of 6 NCB MFMAs with no branch, cut into
+    // scheduling regions per 32-channel block: the block's first MFMA, then the NEXT block's two A reads (into the
+    // other of two register sets), then its other two MFMAs, so a read has two MFMAs to return before the wait in
+    // front of the next block; blocks 0 and 2 of chunk 0 also split one quad each of chunk 1 into a second B set.
+    // Only the stage's first A read and the split of chunk 0 stand in front of an MFMA.  Every accumulator takes
+    // its MFMAs as before: chunk-ascending, passes hi*hi, hi*lo, lo*hi.
+    // !FULL (a partial group, nact < NCB live blocks): the plain loop, which leaves the empty blocks out.
+    // The padded iterations of the ring (st > last) only keep the loads and the barrier in step.
+    auto mainloop = [&](auto fullc) {
+        constexpr bool FULL = decltype(fullc)::value;
+        for (int s0 = 0; s0 < npad; s0 += D) {
+            static_for<D>([&](auto jc) {
+                constexpr int j = decltype(jc)::value;
+                constexpr int jn = (j + D - 1) % D;
+                const int st = s0 + j;
+                // the weights of stage st + 1 -> the other buffer (its readers passed the previous barrier), then the
+                // input of stage st + D - 1
+                wdma(min(st + 1, last), (st + 1) & 1);
+                __builtin_amdgcn_sched_barrier(0);
+                issue(min(st + D - 1, last), st + D - 1 <= last, raw[jn]);
+                __builtin_amdgcn_sched_barrier(0);
+                const char* wb = wl + (st & 1) * WSTAGE + lane * 16;
+                if (st > last) {
+                    // (a padded iteration of the ring: its input is zero, nothing to add)
+                } else if constexpr (FULL) {
+                    f16x8 A[2][2], Bh[2], Bl[2];
+                    f16x4 qh[2], ql[2];
+                    auto loadA = [&](int i, f16x8 (&d)[2]) __attribute__((always_inline)) {  // block i = k * NCB + cb
+                        d[0] = *reinterpret_cast<const f16x8*>(wb + i * 2048);
+                        d[1] = *reinterpret_cast<const f16x8*>(wb + i * 2048 + 1024);
+                    };
+                    loadA(0, A[0]);
+                    splitQ(st, 0, 0, raw[j], qh[0], ql[0]);
+                    splitQ(st, 0, 1, raw[j], qh[1], ql[1]);
+                    Bh[0] = cat8(qh[0], qh[1]);
+                    Bl[0] = cat8(ql[0], ql[1]);
+                    __builtin_amdgcn_sched_barrier(0);
+                    static_for<2 * NCB>([&](auto ic) {
+                        constexpr int i = decltype(ic)::value;
+                        constexpr int k = i / NCB, cb = i - k * NCB;
+                        acc[cb] = X3_MFMA(A[i & 1][0], Bh[k], acc[cb], 0, 0, 0);
+                        __builtin_amdgcn_sched_barrier(0);
+                        if constexpr (i + 1 < 2 * NCB) loadA(i + 1, A[(i + 1) & 1]);
+                        __builtin_amdgcn_sched_barrier(0);
+                        if constexpr (i == 0) splitQ(st, 1, 0, raw[j], qh[0], ql[0]);
+                        if constexpr (i == 2) {
+                            splitQ(st, 1, 1, raw[j], qh[1], ql[1]);
+                            Bh[1] = cat8(qh[0], qh[1]);
+                            Bl[1] = cat8(ql[0], ql[1]);
                         }
-                        v0[e] = live ? y0 : 0.f;  // (outside the frame: the conv's zero padding)
-                        v1[e] = live ? y1 : 0.f;
+                        acc[cb] = X3_MFMA(A[i & 1][0], Bl[k], acc[cb], 0, 0, 0);
+                        acc[cb] = X3_MFMA(A[i & 1][1], Bh[k], acc[cb], 0, 0, 0);
+                        __builtin_amdgcn_sched_barrier(0);
+                    });
+                } else {
+#pragma unroll
+                    for (int k = 0; k < 2; ++k) {
+                        f16x4 h0, l0, h1, l1;
+                        splitQ(st, k, 0, raw[j], h0, l0);
+                        splitQ(st, k, 1, raw[j], h1, l1);
+                        const f16x8 Bh = cat8(h0, h1), Bl = cat8(l0, l1);
+#pragma unroll
+                        for (int cb = 0; cb < NCB; ++cb) {
+                            if (cb >= nact) break;  // (uniform: a tail group's empty blocks)
+                            const f16x8 Ah = *reinterpret_cast<const f16x8*>(wb + (k * NCB + cb) * 2048);
+                            const f16x8 Al = *reinterpret_cast<const f16x8*>(wb + (k * NCB + cb) * 2048 + 1024);
+                            acc[cb] = X3_MFMA(Ah, Bh, acc[cb], 0, 0, 0);
+                            acc[cb] = X3_MFMA(Ah, Bl, acc[cb], 0, 0, 0);
+                            acc[cb] = X3_MFMA(Al, Bh, acc[cb], 0, 0, 0);
+                        }
                     }
                 }
-                if (scaled) {
-                    v0 *= xs;
-                    v1 *= xs;
-                }
-                split4(v0, h0, l0);
-                split4(v1, h1, l1);
-                const f16x8 Bh = f16x8{h0[0], h0[1], h0[2], h0[3], h1[0], h1[1], h1[2], h1[3]};
-                const f16x8 Bl = f16x8{l0[0], l0[1], l0[2], l0[3], l1[0], l1[1], l1[2], l1[3]};
-#pragma unroll
-                for (int cb = 0; cb < NCB; ++cb) {
-                    if (cb >= nact) break;  // (uniform: a tail group's empty blocks)
-                    const f16x8 Ah = *reinterpret_cast<const f16x8*>(wb + (k * NCB + cb) * 2048);
-                    const f16x8 Al = *reinterpret_cast<const f16x8*>(wb + (k * NCB + cb) * 2048 + 1024);
-                    acc[cb] = X3_MFMA(Ah, Bh, acc[cb], 0, 0, 0);
-                    acc[cb] = X3_MFMA(Ah, Bl, acc[cb], 0, 0, 0);
-                    acc[cb] = X3_MFMA(Al, Bh, acc[cb], 0, 0, 0);
-                }
-            }
-            __syncthreads();
-        });
-    }
+                wsync();
+            });
+        }
+    };
+    if (nact == NCB)
+        mainloop(std::true_type{});
+    else
+        mainloop(std::false_type{});
     const float inv = 1.f / (pow2_scale_for(a.wpack[packed_body(a.Cout, a.Cin, 1)]) * xs);
     if constexpr (!PRO) {
         if (a.spec_z != nullptr) {
@@ -1285,7 +1349,7 @@ int nps_launch_conv2d_x3(const nps_conv2d_t& a, int lds, hipStream_t s) {
             const long nb = ((long)a.Hout * a.Wout + 127) / 128;
             NPS_CHECK_ARG(nb < (1L << 31) && a.B < 65536, "conv2d_fwd: grid too large");
             const int ncp = ((a.Cin + 31) / 32) * 32;
-            conv1x1_wl_kernel<6, 2, true><<<dim3((unsigned)nb, a.B), 256, 2 * 2 * 6 * 2048 + 6 * 32 * 4 + 2 * ncp * 4, s>>>(a, 1);
+            conv1x1_wl_kernel<6, 3, true><<<dim3((unsigned)nb, a.B), 256, 2 * 2 * 6 * 2048 + 6 * 32 * 4 + 2 * ncp * 4, s>>>(a, 1);
             NPS_CHECK_LAUNCH("conv2d_fwd (split-fp16 1x1, LDS weights, GroupNorm prologue)");
             return 0;
         }
@@ -1297,8 +1361,9 @@ int nps_launch_conv2d_x3(const nps_conv2d_t& a, int lds, hipStream_t s) {
             long nb = ((long)a.Hout * a.Wout + 127) / 128;
             if (ng > 1) nb = (nb + 7) / 8 * 8 * ng;
             NPS_CHECK_ARG(nb < (1L << 31) && a.B < 65536, "conv2d_fwd: grid too large");
-            // B-ring depth 2: measured fastest on every rollout shape (profiles/r1_conv_shapes_1x1_wl_depth.log)
-            conv1x1_wl_kernel<6, 2><<<dim3((unsigned)nb, a.B), 256, 2 * 2 * 6 * 2048 + 6 * 32 * 4, s>>>(a, ng);
+            // B-ring depth 3 (two stages of input in flight): 1x1 class 14.5 -> 14.0 ms per call over depth 2;
+            // depth 4 measured no faster, and spills the prologue kernel (profiles/x1_pipeline/steps.txt)
+            conv1x1_wl_kernel<6, 3><<<dim3((unsigned)nb, a.B), 256, 2 * 2 * 6 * 2048 + 6 * 32 * 4, s>>>(a, ng);
             NPS_CHECK_LAUNCH("conv2d_fwd (split-fp16 1x1, LDS weights)");
             return 0;
         }
@@ -1360,7 +1425,7 @@ extern "C" long nps_conv2d_x3_weight_span(const nps_conv2d_t* ap) {
             // conv1x1_res_kernel: chunks [0, nres), blocks [0, ng * NCB) (group grp at grp * NCB)
             top((rnres - 1) * gstride + (long)rng * rncb * 2048);
         } else if (a.Cout <= 192 || g_x1_groups) {
-            // conv1x1_wl_kernel<6, *>: wfetch(min(st + 2, last)) -> chunks 2 last + 1, 6 blocks of the chunk at
+            // conv1x1_wl_kernel<6, *>: wdma(min(st + 1, last)) -> chunks 2 last + 1, 6 blocks of the chunk at
             // its group's offset (ng groups of 6 blocks)
             top((2 * nst - 1) * gstride + (long)((a.Cout + 191) / 192) * 6 * 2048);
         } else {
