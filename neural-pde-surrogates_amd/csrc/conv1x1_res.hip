@@ -12,10 +12,11 @@
 // flight per wave, 8 waves per CU), and stores each block from the accumulators with the fused epilogue of
 // conv1x1_wl_kernel (bias from LDS, one addend, GELU, GroupNorm moments, range tag).  Waves drift apart, so one
 // wave's epilogue stores overlap the other waves' loads and MFMAs.
-//   * ng = 1, NCB = 6: Cout <= 192 and Cin <= 208 (13 chunks x 12 KiB).
-//   * ng = 2: the output channels split over two work-groups of one XCD (consecutive ranks on XCD blockIdx % 8)
-//     that walk the SAME pixel blocks, so the second reads the input from that XCD's L2: NCB = 3 for Cout <= 192,
-//     Cin <= 416 (the U-Net's 388-channel shortcut); NCB = 4 for 192 < Cout <= 256, Cin <= 304 (the decoder's 225).
+//   * One instantiation ships, for the one shape class where this wins (nps_conv1x1_res_plan): the planar decoder
+//     1x1 with 192 < Cout <= 256 (225) and Cin <= 304, as NCB = 4, ng = 2 — the output channels split over two
+//     work-groups of one XCD (consecutive ranks on XCD blockIdx % 8) that walk the SAME pixel blocks, so the second
+//     reads the input from that XCD's L2.  (NCB = 6 / ng = 1 and NCB = 3 / ng = 2 for Cout <= 192 measured at par or
+//     slower than conv1x1_wl_kernel: DESIGN.md, retired knobs.)
 //   * The last stage's second chunk stays out of LDS when it holds no input channel.
 //   * Stage, chunk and fragment math is conv1x1_wl_kernel's (the ntaps == 1 packing of pack_weights_x3_kernel), and
 //     the epilogue keeps store_tile's float order, so both kernels give bit-identical outputs.
@@ -290,51 +291,31 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(2))) void c
     nps::tag_publish(a.out_tag, amax, nps::wave_salt());
 }
 
-template <int NCB, int D>
-void launch(const nps_conv2d_t& a, unsigned grid, int ng, int nres, hipStream_t s) {
-    static bool attr_set = false;
-    if (!attr_set) {
-        (void)hipFuncSetAttribute((const void*)conv1x1_res_kernel<NCB, D>, hipFuncAttributeMaxDynamicSharedMemorySize,
-                                  160 * 1024);
-        attr_set = true;
-    }
-    conv1x1_res_kernel<NCB, D><<<grid, 512, x1r_lds_bytes(NCB, nres), s>>>(a, ng, nres);
-}
-
 }  // namespace
 
-int nps_conv1x1_res_plan(const nps_conv2d_t& a, int all, int* ncb, int* ng, int* nres) {
-    // all = 0: only the planar (NCHW) 1x1s with 192 < Cout <= 256 — the decoder's pre-output, which the LDS-staged
-    // kernel (Cout <= 192, NHWC) cannot take and the co-block kernel ran at 1.4 TB/s; all = 1 (dev knob
-    // NPS_X1_RES=1): every eligible 1x1
-    if (!all && !(a.out_nchw && a.Cout > 192 && a.Cout <= 256)) return 0;
-    if (a.KH * a.KW != 1 || a.accumulate || a.addend1 != nullptr || a.gn_stats != nullptr || a.pre_act != 0 ||
-        a.spec_z != nullptr)
+// The one shape class that runs here: channel blocks per group, channel groups, register-ring depth
+constexpr int X1R_NCB = 4, X1R_NG = 2, X1R_D = 4;
+
+int nps_conv1x1_res_plan(const nps_conv2d_t& a, int* ncb, int* ng, int* nres) {
+    // only the planar (NCHW) 1x1s with 192 < Cout <= 256 — the decoder's pre-output, which conv1x1_wl_kernel's
+    // store_tile epilogue writes one strided element at a time.  Resident weights for every eligible 1x1 measured
+    // at par or slower (profiles/r5/experiments/x1_resident_weights_ab.txt)
+    if (!(a.out_nchw && a.Cout > 192 && a.Cout <= 256)) return 0;
+    if (a.KH * a.KW != 1 || a.accumulate || a.addend0 != nullptr || a.addend1 != nullptr || a.out_stats != nullptr ||
+        a.gn_stats != nullptr || a.pre_act != 0 || a.spec_z != nullptr)
         return 0;
-    if (a.out_nchw && (a.addend0 != nullptr || a.out_stats != nullptr)) return 0;
-    if (a.out_stats != nullptr && a.Cout > 192) return 0;  // (moments of the stored values: addend / act included)
     if ((long)a.B * ((a.Hout * a.Wout + 31) / 32) >= (1L << 31)) return 0;
     const int nr = x1r_nres(a.Cin);
-    const int lmax = 160 * 1024;
-    int c = 0, g = 0;
-    if (a.Cout <= 192 && x1r_lds_bytes(6, nr) <= lmax) {
-        c = 6, g = 1;
-    } else if (a.Cout <= 192 && x1r_lds_bytes(3, nr) <= lmax) {
-        c = 3, g = 2;
-    } else if (a.Cout > 192 && a.Cout <= 256 && x1r_lds_bytes(4, nr) <= lmax) {
-        c = 4, g = 2;
-    } else {
-        return 0;
-    }
-    *ncb = c;
-    *ng = g;
+    if (x1r_lds_bytes(X1R_NCB, nr) > 160 * 1024) return 0;  // Cin <= 304
+    *ncb = X1R_NCB;
+    *ng = X1R_NG;
     *nres = nr;
     return 1;
 }
 
-int nps_launch_conv1x1_res(const nps_conv2d_t& a, int all, hipStream_t s) {
+int nps_launch_conv1x1_res(const nps_conv2d_t& a, hipStream_t s) {
     int ncb = 0, ng = 0, nres = 0;
-    if (!nps_conv1x1_res_plan(a, all, &ncb, &ng, &nres)) return 0;
+    if (!nps_conv1x1_res_plan(a, &ncb, &ng, &nres)) return 0;
     static long gx = 0;
     if (gx == 0) {
         int dev = 0, n = 0;
@@ -343,11 +324,12 @@ int nps_launch_conv1x1_res(const nps_conv2d_t& a, int all, hipStream_t s) {
             n = 256;
         gx = n & ~15;  // persistent: one work-group per CU, a multiple of 16 (8 XCDs x 2 channel groups)
     }
-    if (ncb == 6)
-        launch<6, 3>(a, (unsigned)gx, 1, nres, s);
-    else if (ncb == 3)
-        launch<3, 4>(a, (unsigned)gx, 2, nres, s);
-    else
-        launch<4, 4>(a, (unsigned)gx, 2, nres, s);
+    static bool attr_set = false;
+    if (!attr_set) {
+        (void)hipFuncSetAttribute((const void*)conv1x1_res_kernel<X1R_NCB, X1R_D>,
+                                  hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
+        attr_set = true;
+    }
+    conv1x1_res_kernel<X1R_NCB, X1R_D><<<(unsigned)gx, 512, x1r_lds_bytes(X1R_NCB, nres), s>>>(a, ng, nres);
     return 1;
 }

@@ -504,8 +504,8 @@ __device__ __forceinline__ void pack_x3_pair(const float* __restrict__ w, _Float
     const int tap = r % ntaps; r /= ntaps;
     const int chunk = (int)r;
     // 1x1: chunk pair (2s, 2s + 1) covers channels [32s, 32s + 32) with lane half h holding the contiguous
-    // run [32s + 16h, 32s + 16h + 16): chunk 2s its first 8, chunk 2s + 1 its last 8 (conv1x1_x3_kernel
-    // fetches 64 contiguous bytes per lane); other tap counts: chunk c = channels [16c, 16c + 16)
+    // run [32s + 16h, 32s + 16h + 16): chunk 2s its first 8, chunk 2s + 1 its last 8 (the 1x1 kernels
+    // fetch 64 contiguous bytes per lane); other tap counts: chunk c = channels [16c, 16c + 16)
     const int ci = ntaps == 1 && (tphase == -1 || tphase == -3) ? (chunk >> 1) * 32 + (lane >> 5) * 16 + (chunk & 1) * 8 + j
                                               : chunk * CK + (lane >> 5) * 8 + j;
     const float v = pow2_scale_for(m) * weight_elem(w, Cout, Cin, KH, KW, tphase, cb * 32 + (lane & 31), ci, tap);
@@ -758,26 +758,16 @@ extern "C" int nps_conv2d_plan(nps_conv2d_t* a) {
         // work-groups over the 256 CUs; 256-pixel tiles carry a 10 % penalty (half the reuse of
         // each weight fragment per global load)
         // Wide tiles (16x8, 8x16, 4x32 pixels x 192 channels) replace them for 2x2 / 3x3 convs with
-        // 128 < Cout <= 192: one staged patch feeds all the output channels (dev knob NPS_X3_WIDE=0: off).
-        static int wide_on = -1;
-        if (wide_on < 0) {
-            const char* e = getenv("NPS_X3_WIDE");
-            wide_on = (e != nullptr && e[0] == '0') ? 0 : 1;
-        }
+        // 128 < Cout <= 192: one staged patch feeds all the output channels (NPS_X3_WIDE=0: off).
+        static const bool wide_on = nps::env_flag("NPS_X3_WIDE", true);
         const bool wide = wide_on && x3_wide_eligible(*a);
-        // wide candidates in preference order: 16x8 first (same-box A/B at C3: 3x3 class -1.7 % against 8x16,
-        // equal FETCH_SIZE; profiles/r2s2/tile_ab)
-        const int cand[9][2] = {{16, 32}, {32, 16}, {8, 64}, {16, 16}, {8, 32}, {16, 8}, {8, 16}, {4, 32}, {32, 4}};
+        // the first five are the narrow tiles, the last three the wide ones in preference order: 16x8 first
+        // (same-box A/B at C3: 3x3 class -1.7 % against 8x16, equal FETCH_SIZE; profiles/r2s2/tile_ab)
+        const int cand[8][2] = {{16, 32}, {32, 16}, {8, 64}, {16, 16}, {8, 32}, {16, 8}, {8, 16}, {4, 32}};
         const long units = wide ? (a->Cout + 191) / 192 : units_co;
-        static int wide_tile = -2;  // dev knob NPS_X3_WIDE_TILE=0/1/2/3: force 16x8 / 8x16 / 4x32 / 32x4 wide tiles
-        if (wide_tile == -2) {
-            const char* e = getenv("NPS_X3_WIDE_TILE");
-            wide_tile = (e != nullptr && e[0] >= '0' && e[0] <= '3') ? e[0] - '0' : -1;
-        }
         int best = -1;
         double best_eff = -1.0;
-        for (int i = wide ? 5 : 0; i < (wide ? (wide_tile == 3 ? 9 : 8) : 5); ++i) {
-            if (wide && wide_tile >= 0 && i != 5 + wide_tile) continue;
+        for (int i = wide ? 5 : 0; i < (wide ? 8 : 5); ++i) {
             nps_conv2d_t t = *a;
             t.waves = 8;
             t.TH = cand[i][0];

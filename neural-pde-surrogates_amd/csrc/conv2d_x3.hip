@@ -573,278 +573,18 @@ __global__ __launch_bounds__(512) void conv2d_x3_kernel(const nps_conv2d_t a) {
     nps::tag_publish(a.out_tag, amax, nps::wave_salt());
 }
 
-
 // ---------------------------------------------------------------------------------------------
-// Split-fp16 1x1 conv without a patch ring: every wave is its own producer.  A 1x1 stage has 9x less
-// MFMA work per staged byte than a 3x3 one, so the ring kernel's single fetch in flight per work-group
-// leaves it bound by HBM latency.  Here a work-group is up to 8 waves over the same PB * 32 output
-// pixels (wave w: output channels [co_lo + 64w, + 64), co_lo = 512 * blockIdx.z), each wave streaming
-// its B fragments straight from HBM into a D-deep register ring with no barrier; the co-block waves of
-// a work-group read the same bytes (one HBM fetch, L1/L2 hits).  A stage is 32 channels: lane half h
-// fetches the contiguous run [32s + 16h, + 16) of its pixel (64 B, four 16-B loads), which feeds two
-// K-groups — the packing (pack_weights_x3_kernel, ntaps == 1) orders the weights to match.  The
-// weights stream from L2 one stage ahead.  MFMA passes hi*hi, hi*lo, lo*hi as the ring kernel; the
-// epilogue goes through LDS (one contiguous channel run per pixel) or store_tile.
-
-template <int PB, int D>
-__global__ __launch_bounds__(512) void conv1x1_x3_kernel(const nps_conv2d_t a) {
-    constexpr int CBW = 2;
-    const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
-    const int co_lo = blockIdx.z * 512;
-    const int cob = (co_lo >> 6) + wv;  // global 64-channel block of this wave
-    const int b = blockIdx.y;
-    const int h = lane >> 5;
-    const int npx = a.Hout * a.Wout;
-    const int P0 = blockIdx.x * (PB * 32);
-    const float xs = in_scale_of(a);
-    const bool scaled = has_in_scale(a);  // range-scaled input (xs != 1 possible)
-    // this lane's output pixel of each pixel block -> its (circularly extended) frame position
-    int fy[PB], fx[PB];
-    unsigned pin = 0;
-#pragma unroll
-    for (int pb = 0; pb < PB; ++pb) {
-        const int P = P0 + pb * 32 + (lane & 31);
-        const int oy = P / a.Wout, ox = P - (P / a.Wout) * a.Wout;
-        const int ye = oy - a.pad_y, xe = ox - a.pad_x;
-        const bool ok = P < npx && ye >= 0 && ye < a.Hin + 2 * a.circ && xe >= 0 && xe < a.Win + 2 * a.circ;
-        fy[pb] = a.circ ? nps::wrap_mod(ye - a.circ, a.Hin) : ye;
-        fx[pb] = a.circ ? nps::wrap_mod(xe - a.circ, a.Win) : xe;
-        pin = ok ? (pin | (1u << pb)) : pin;
-    }
-    const float* sp[PB];  // this lane's pixel in its current source (x3_zero16 when outside it)
-    int cur_src = -1;     // per lane: the two lane halves may read different sources
-    int cbase = 0;
-    auto locate = [&](int sidx) {
-        const nps_src_t S0 = a.src[0], S1 = a.src[1], S2 = a.src[2];
-        const float* sptr = sidx == 0 ? S0.ptr : (sidx == 1 ? S1.ptr : S2.ptr);
-        const int sC = sidx == 0 ? S0.C : (sidx == 1 ? S1.C : S2.C);
-        const int sH = sidx == 0 ? S0.H : (sidx == 1 ? S1.H : S2.H);
-        const int sW = sidx == 0 ? S0.W : (sidx == 1 ? S1.W : S2.W);
-        const int soy = sidx == 0 ? S0.off_y : (sidx == 1 ? S1.off_y : S2.off_y);
-        const int sox = sidx == 0 ? S0.off_x : (sidx == 1 ? S1.off_x : S2.off_x);
-#pragma unroll
-        for (int pb = 0; pb < PB; ++pb) {
-            const int yy = fy[pb] - soy, xx = fx[pb] - sox;
-            const bool ok = ((pin >> pb) & 1u) && yy >= 0 && yy < sH && xx >= 0 && xx < sW;
-            sp[pb] = ok ? sptr + ((size_t)(b * sH + yy) * sW + xx) * sC : nullptr;
-        }
-    };
-    const int nstages = (a.Cin + 2 * CK - 1) / (2 * CK);  // 32-channel stages
-    const int last = nstages - 1;
-    f32x4 raw[D][PB][4];  // register ring of B stages (fp32, as loaded; zeros outside the frame)
-    auto issue = [&](int st, bool live, f32x4 (&r)[PB][4]) {
-        const int c0 = st * 2 * CK + h * CK;  // this lane half's 16-channel run (inside one source:
-        int sidx = 0, lo = 0, sb = 0;         // sources are 16-aligned, host-checked)
-#pragma unroll
-        for (int si = 0; si < NPS_MAX_SRC; ++si) {
-            if (si < a.nsrc) {
-                const int hi = lo + a.src[si].C;
-                if (c0 >= lo && c0 < hi) {
-                    sidx = si;
-                    sb = lo;
-                }
-                lo = hi;
-            }
-        }
-        if (sidx != cur_src) {  // per lane (the halves of a wave may differ)
-            locate(sidx);
-            cur_src = sidx;
-            cbase = sb;
-        }
-#pragma unroll
-        for (int q = 0; q < 4; ++q) {
-            const bool chok = live && c0 + q * 4 < a.Cin;  // past the channel tail (or a padded stage): zeros
-#pragma unroll
-            for (int pb = 0; pb < PB; ++pb) {
-                const float* src = (chok && sp[pb] != nullptr) ? sp[pb] + (c0 - cbase + q * 4) : x3_zero16;
-                r[pb][q] = *reinterpret_cast<const f32x4*>(src);
-            }
-        }
-    };
-    const int ncb = packed_ncb(a.Cout);
-    const size_t gstride = (size_t)ncb * 2048;  // bytes per chunk of the packed weight
-    // the last 512-channel group's waves past the packed blocks (Cout = 600: 12 packed 64-channel blocks, waves
-    // of blocks 12-15) read the last packed block instead of bytes past the buffer; they store nothing
-    // (co >= Cout in either epilogue)
-    const int wcob = cob < ncb / CBW ? cob : ncb / CBW - 1;
-    const char* wbase = reinterpret_cast<const char*>(a.wpack) + (size_t)wcob * CBW * 2048 + lane * 16;
-    f16x8 Aw[2][2][CBW][2];  // [slot][chunk of the pair][cb][hi, lo]
-    auto loadA = [&](int st, f16x8 (&d)[2][CBW][2]) {
-#pragma unroll
-        for (int k = 0; k < 2; ++k) {
-            const char* p = wbase + (size_t)(2 * st + k) * gstride;
-#pragma unroll
-            for (int cb = 0; cb < CBW; ++cb) {
-                d[k][cb][0] = *reinterpret_cast<const f16x8*>(p + cb * 2048);
-                d[k][cb][1] = *reinterpret_cast<const f16x8*>(p + cb * 2048 + 1024);
-            }
-        }
-    };
-    f32x16 acc[CBW][PB];
-#pragma unroll
-    for (int i = 0; i < CBW; ++i)
-#pragma unroll
-        for (int j = 0; j < PB; ++j)
-#pragma unroll
-            for (int r = 0; r < 16; ++r) acc[i][j][r] = 0.f;
-    // the stage loop runs a multiple of D stages so its body is straight-line (a per-stage guard makes the
-    // compiler's wait at the guard's join vmcnt(0)); padded stages fetch the last stage again with an
-    // all-zero mask, so their MFMAs add exact zeros
-    static_for<D - 1>([&](auto jc) {
-        constexpr int j = decltype(jc)::value;
-        issue(min(j, last), j <= last, raw[j]);
-    });
-    loadA(0, Aw[0]);
-    const int npad = (nstages + D - 1) / D * D;
-    for (int s0 = 0; s0 < npad; s0 += D) {
-        static_for<D>([&](auto jc) {
-            constexpr int j = decltype(jc)::value;
-            constexpr int jn = (j + D - 1) % D;
-            const int st = s0 + j;
-            issue(min(st + D - 1, last), st + D - 1 <= last, raw[jn]);
-            loadA(min(st + 1, last), Aw[(j + 1) & 1]);
-            // keep the new fetches ahead of this stage's MFMAs: sunk below them, the MFMAs' wait for
-            // this stage's operands would become vmcnt(0) and drain the whole ring every stage
-            __builtin_amdgcn_sched_barrier(0);
-            constexpr int r = j & 1;  // D is even: the weight slot parity is static
-#pragma unroll
-            for (int k = 0; k < 2; ++k) {  // the two K-groups of the stage: floats [8k, 8k + 8) of the run
-                f16x8 Bh[PB], Bl[PB];
-#pragma unroll
-                for (int pb = 0; pb < PB; ++pb) {
-                    f16x4 h0, l0, h1, l1;
-                    f32x4 v0 = raw[j][pb][2 * k], v1 = raw[j][pb][2 * k + 1];
-                    if (scaled) {
-                        v0 *= xs;
-                        v1 *= xs;
-                    }
-                    split4(v0, h0, l0);
-                    split4(v1, h1, l1);
-                    Bh[pb] = f16x8{h0[0], h0[1], h0[2], h0[3], h1[0], h1[1], h1[2], h1[3]};
-                    Bl[pb] = f16x8{l0[0], l0[1], l0[2], l0[3], l1[0], l1[1], l1[2], l1[3]};
-                }
-#pragma unroll
-                for (int cb = 0; cb < CBW; ++cb)
-#pragma unroll
-                    for (int pb = 0; pb < PB; ++pb)
-                        acc[cb][pb] = X3_MFMA(Aw[r][k][cb][0], Bh[pb], acc[cb][pb], 0, 0, 0);
-#pragma unroll
-                for (int cb = 0; cb < CBW; ++cb)
-#pragma unroll
-                    for (int pb = 0; pb < PB; ++pb)
-                        acc[cb][pb] = X3_MFMA(Aw[r][k][cb][0], Bl[pb], acc[cb][pb], 0, 0, 0);
-#pragma unroll
-                for (int cb = 0; cb < CBW; ++cb)
-#pragma unroll
-                    for (int pb = 0; pb < PB; ++pb)
-                        acc[cb][pb] = X3_MFMA(Aw[r][k][cb][1], Bh[pb], acc[cb][pb], 0, 0, 0);
-            }
-        });
-    }
-    const float inv = 1.f / (pow2_scale_for(a.wpack[packed_body(a.Cout, a.Cin, 1)]) * xs);
-    if (x3_lds_epilogue(a)) {
-        // the work-group's (waves*64) x PB*32 tile goes through LDS (pitch = waves*64 + 4 floats: conflict-
-        // free 16-B writes) and is stored pixel by pixel, each pixel's channels one contiguous run
-        extern __shared__ __attribute__((aligned(16))) float T[];
-        const int pitch = (int)(blockDim.x) + 4;  // blockDim.x = 64 * waves
-#pragma unroll
-        for (int pb = 0; pb < PB; ++pb) {
-            const int P = pb * 32 + (lane & 31);
-#pragma unroll
-            for (int cb = 0; cb < CBW; ++cb)
-#pragma unroll
-                for (int m = 0; m < 4; ++m) {
-                    const f32x4 v = {acc[cb][pb][4 * m] * inv, acc[cb][pb][4 * m + 1] * inv,
-                                     acc[cb][pb][4 * m + 2] * inv, acc[cb][pb][4 * m + 3] * inv};
-                    *reinterpret_cast<f32x4*>(T + P * pitch + wv * 64 + cb * 32 + 8 * m + 4 * h) = v;
-                }
-        }
-        __syncthreads();
-        const int nco = min(a.Cout - co_lo, (int)blockDim.x);
-        const int C4 = nco >> 2;
-        // item i = (pixel p, channel quad): when C4 divides the block, a thread keeps one channel quad
-        // and steps pixels by blockDim / C4 (no per-item divisions)
-        const bool fixq = ((int)blockDim.x % C4) == 0;
-        const int pstep = fixq ? (int)blockDim.x / C4 : 0;
-        int fp = fixq ? (int)threadIdx.x / C4 : 0;
-        const int fcl = fixq ? ((int)threadIdx.x - fp * C4) * 4 : 0;
-        int foy = (P0 + fp) / a.Wout, fox = (P0 + fp) - ((P0 + fp) / a.Wout) * a.Wout;
-        float amax = 0.f;
-        for (int i = threadIdx.x; i < PB * 32 * C4; i += blockDim.x) {
-            int p, cl, oy, ox;
-            if (fixq) {
-                p = fp;
-                cl = fcl;
-                oy = foy;
-                ox = fox;
-                fp += pstep;
-                fox += pstep;
-                while (fox >= a.Wout) {
-                    fox -= a.Wout;
-                    ++foy;
-                }
-            } else {
-                p = i / C4;
-                cl = (i - (i / C4) * C4) * 4;
-                oy = (P0 + p) / a.Wout;
-                ox = (P0 + p) - ((P0 + p) / a.Wout) * a.Wout;
-            }
-            const int co0 = co_lo + cl;
-            const int P = P0 + p;
-            if (P >= npx) continue;
-            const int dy = oy * a.out_os + a.out_off_y, dx = ox * a.out_os + a.out_off_x;
-            if (dy < 0 || dy >= a.out_H || dx < 0 || dx >= a.out_W) continue;
-            const f32x4 accv = *reinterpret_cast<const f32x4*>(T + p * pitch + cl);
-            const size_t o = (((size_t)b * a.out_H + dy) * a.out_W + dx) * a.out_C + co0;
-            const f32x4 z = {0.f, 0.f, 0.f, 0.f};
-            const f32x4 bi = a.bias ? *reinterpret_cast<const f32x4*>(a.bias + co0) : z;
-            const f32x4 a0 = a.addend0 ? *reinterpret_cast<const f32x4*>(a.addend0 + o) : z;
-            const f32x4 a1 = a.addend1 ? *reinterpret_cast<const f32x4*>(a.addend1 + o) : z;
-            const f32x4 ov = a.accumulate ? *reinterpret_cast<const f32x4*>(a.out + o) : z;
-            f32x4 r;
-#pragma unroll
-            for (int e = 0; e < 4; ++e) {  // as store_tile / x3_store_phase
-                float v = accv[e] + bi[e];
-                if (!a.add_after_act) v = v + a0[e] + a1[e];
-                if (a.act == 1) v = nps::gelu_erf(v);
-                if (a.add_after_act) v = v + a0[e] + a1[e];
-                if (a.accumulate) v += ov[e];
-                r[e] = v;
-                amax = fmaxf(amax, fabsf(v));
-            }
-            *reinterpret_cast<f32x4*>(a.out + o) = r;
-        }
-        nps::tag_publish(a.out_tag, amax, nps::wave_salt());
-        return;
-    }
-    float amax = 0.f;
-    static_for<PB>([&](auto pbc) {  // compile-time pb: acc stays in registers
-        constexpr int pb = decltype(pbc)::value;
-        const int P = P0 + pb * 32 + (lane & 31);
-        if (P >= npx) return;
-        const int oy = P / a.Wout, ox = P - (P / a.Wout) * a.Wout;
-        const int dy = oy * a.out_os + a.out_off_y, dx = ox * a.out_os + a.out_off_x;
-        if (dy < 0 || dy >= a.out_H || dx < 0 || dx >= a.out_W) return;
-#pragma unroll
-        for (int cb = 0; cb < CBW; ++cb) {
-            const int co = cob * 64 + cb * 32;
-            if (co >= a.Cout) continue;
-            f32x16 v = acc[cb][pb];
-#pragma unroll
-            for (int r = 0; r < 16; ++r) v[r] *= inv;
-            store_tile(a, b, co, h, v, dy, dx, amax);
-        }
-    });
-    nps::tag_publish(a.out_tag, amax, nps::wave_salt());
-}
-
-// 1x1 with the weights staged in LDS: a wave covers ALL output channels (NCB 32-channel blocks) of its
-// 32 pixels, so a work-group of 4 waves (128 pixels) fetches its input once per CU instead of once per
-// co-block wave.  Per 32-channel stage the 4 waves copy the stage's weight fragments (2 chunks x NCB
-// blocks x 2 KB) into one of two LDS buffers by LDS-DMA (one stage ahead, no staging registers), one
-// barrier per stage; B as in conv1x1_x3_kernel (per-lane 64-B runs in a D-deep register ring, zero page
-// outside the frame): D - 1 stages of input stay in flight, D - 2 of them across the stage barrier, which
-// waits for the DMA with a counted vmcnt.  Epilogue: store_tile per 32-channel block.
+// Split-fp16 1x1 conv without a patch ring: a 1x1 stage has 9x less MFMA work per staged byte than a 3x3 one, so
+// the ring kernel's single fetch in flight per work-group leaves it bound by HBM latency.  Here every wave streams
+// its own input (B) straight from HBM and the weights are staged in LDS: a wave covers ALL output channels (NCB
+// 32-channel blocks) of its 32 pixels, so a work-group of 4 waves (128 pixels) fetches its input once per CU.
+// A stage is 32 channels: lane half h fetches the contiguous run [32s + 16h, + 16) of its pixel (64 B, four 16-B
+// loads, zero page outside the frame) into a D-deep register ring; the run feeds two K-groups, and the packing
+// (pack_weights_x3_kernel, ntaps == 1) orders the weights to match.  Per stage the 4 waves copy the stage's weight
+// fragments (2 chunks x NCB blocks x 2 KB) into one of two LDS buffers by LDS-DMA (one stage ahead, no staging
+// registers), one barrier per stage: D - 1 stages of input stay in flight, D - 2 of them across the stage barrier,
+// which waits for the DMA with a counted vmcnt.  MFMA passes hi*hi, hi*lo, lo*hi as the ring kernel.  Epilogue:
+// store_tile per 32-channel block.
 // PRO: the frame prologue act(GroupNorm(frame)) (the U-Net's final GN(8) + GELU before its 1x1 conv,
 // proc_unet_modern.py:191-196) applied to each loaded input element before the split, instead of a frame_pack
 // pass: per-channel affine (scale, shift) of this work-group's sample in an LDS table built at kernel start from the
@@ -1283,18 +1023,49 @@ void launch_x3_one(const nps_conv2d_t& a, unsigned nwg, int lds, hipStream_t s) 
 }  // namespace
 
 
-// dev knob NPS_X1_GROUPS=0: 1x1 convs with Cout > 192 on the co-block kernel (conv1x1_x3_kernel) instead of the
-// LDS-weight kernel's channel groups
-static const int g_x1_groups = [] {
-    const char* e = getenv("NPS_X1_GROUPS");
-    return (e != nullptr && e[0] == '0') ? 0 : 1;
-}();
-
 // test hook (nps_x3_set_grid): persistent-grid size override (> 0)
 static long g_x3_grid_override = 0;
 
 extern "C" int nps_x3_set_grid(long wgs) {
     g_x3_grid_override = wgs > 0 ? wgs : 0;
+    return 0;
+}
+
+// 1x1 convs run on the ring-free kernels, whose 32-channel stages match the 1x1 weight packing.  Three arms:
+//   1. fused GroupNorm + GELU prologue (pro): conv1x1_wl_kernel<6, 3, true>, one channel group (Cout <= 192);
+//   2. the planar (NCHW) output with 192 < Cout <= 256 — the decoder's pre-output: resident weights
+//      (conv1x1_res.hip, nps_conv1x1_res_plan);
+//   3. everything else: conv1x1_wl_kernel<6, 3> in ceil(Cout / 192) channel groups.
+// nps_conv2d_x3_weight_span follows the same three arms.
+static int launch_conv1x1(const nps_conv2d_t& a, bool pro, hipStream_t s) {
+    NPS_CHECK_ARG(!pro || a.Cout <= 192, "conv2d_fwd (split-fp16): a 1x1 prologue needs the LDS-weight kernel "
+                  "(Cout <= 192)");
+    NPS_CHECK_ARG(a.spec_z == nullptr || a.Cout <= 192,
+                  "conv2d_fwd (split-fp16 1x1): the fused c2r term needs the LDS-weight kernel");
+    // out_stats: the LDS-weight kernel's fused register epilogue takes the moments of the values it stores
+    // (after the addend and the activation); its store_tile fallback (two addends, accumulate) cannot
+    NPS_CHECK_ARG(a.out_stats == nullptr || (a.Cout <= 192 && !a.accumulate && a.addend1 == nullptr && x3_lds_epilogue(a)),
+                  "conv2d_fwd (split-fp16 1x1): out_stats needs the LDS-weight kernel (Cout <= 192), an NHWC "
+                  "4-aligned output and at most one addend, no accumulate");
+    const long tiles = ((long)a.Hout * a.Wout + 127) / 128;  // 128-pixel work-groups of one sample
+    constexpr int wl_lds = 2 * 2 * 6 * 2048 + 6 * 32 * 4;   // two weight stages of 6 blocks + the bias table
+    if (pro) {  // the per-channel affine table of the sample after the weights
+        NPS_CHECK_ARG(tiles < (1L << 31) && a.B < 65536, "conv2d_fwd: grid too large");
+        const int ncp = ((a.Cin + 31) / 32) * 32;
+        conv1x1_wl_kernel<6, 3, true><<<dim3((unsigned)tiles, a.B), 256, wl_lds + 2 * ncp * 4, s>>>(a, 1);
+        NPS_CHECK_LAUNCH("conv2d_fwd (split-fp16 1x1, LDS weights, GroupNorm prologue)");
+        return 0;
+    }
+    if (nps_launch_conv1x1_res(a, s)) return 0;
+    // Cout > 192 (the input-gradient convs 192 -> 388 / 196): the ng groups of a pixel tile 8 work-groups apart
+    // (one XCD: the later groups read the tile from L2), tiles padded to 8
+    const int ng = (a.Cout + 191) / 192;
+    const long nb = ng > 1 ? (tiles + 7) / 8 * 8 * ng : tiles;
+    NPS_CHECK_ARG(nb < (1L << 31) && a.B < 65536, "conv2d_fwd: grid too large");
+    // B-ring depth 3 (two stages of input in flight): 1x1 class 14.5 -> 14.0 ms per call over depth 2;
+    // depth 4 measured no faster, and spills the prologue kernel (profiles/x1_pipeline/steps.txt)
+    conv1x1_wl_kernel<6, 3><<<dim3((unsigned)nb, a.B), 256, wl_lds, s>>>(a, ng);
+    NPS_CHECK_LAUNCH("conv2d_fwd (split-fp16 1x1, LDS weights)");
     return 0;
 }
 
@@ -1316,66 +1087,12 @@ int nps_launch_conv2d_x3(const nps_conv2d_t& a, int lds, hipStream_t s) {
             n = 256;
         ncu = n;
     }
-    static long per = -1;
-    if (per < 0) {
-        per = (ncu & ~7) > 0 ? (ncu & ~7) : ncu;
-        const char* e = getenv("NPS_X3_GRID");  // dev knob: work-groups of the persistent grid
-        if (e != nullptr && atol(e) > 0) per = atol(e);
-    }
+    const long per = (ncu & ~7) > 0 ? (ncu & ~7) : ncu;
     const long pw = g_x3_grid_override > 0 ? g_x3_grid_override : per;
-    const bool lds_epi = !a.out_nchw && (a.out_C & 3) == 0 && (a.Cout & 3) == 0;  // == x3_lds_epilogue
     const unsigned grid = (unsigned)(pw < nwg ? pw : nwg);  // either epilogue walks tiles (tests: many per WG)
     const bool p512 = a.TH * a.TW == 512;
     const bool pro = a.gn_stats != nullptr || a.pre_act != 0;  // fused frame prologue: 3x3 only (host-checked)
-    // 1x1 convs (never with a prologue: x3_eligible) run on the ring-free kernel, whose 32-channel
-    // stages match the 1x1 weight packing; work-group = min(ncob, 8) waves, blockIdx.z = 512-channel group
-    if (a.KH * a.KW == 1) {
-        NPS_CHECK_ARG(!pro || a.Cout <= 192, "conv2d_fwd (split-fp16): a 1x1 prologue needs the LDS-weight kernel "
-                      "(Cout <= 192)");
-        NPS_CHECK_ARG(a.spec_z == nullptr || a.Cout <= 192,
-                      "conv2d_fwd (split-fp16 1x1): the fused c2r term needs the LDS-weight kernel");
-        const int ncob = (a.Cout + 63) / 64;
-        // out_stats: the LDS-weight kernel's fused register epilogue takes the moments of the values it stores
-        // (after the addend and the activation); its store_tile fallback (two addends, accumulate) cannot
-        NPS_CHECK_ARG(a.out_stats == nullptr || (a.Cout <= 192 && !a.accumulate && a.addend1 == nullptr && lds_epi),
-                      "conv2d_fwd (split-fp16 1x1): out_stats needs the LDS-weight kernel (Cout <= 192), an NHWC "
-                      "4-aligned output and at most one addend, no accumulate");
-        static int res_on = -1;  // dev knob NPS_X1_RES=1: resident-weight kernel for every 1x1 (default: only the
-        if (res_on < 0) {        // planar decoder shape; at par or slower on the others, profiles/r5/experiments/x1_resident_weights_ab.txt)
-            const char* e = getenv("NPS_X1_RES");
-            res_on = (e != nullptr && e[0] == '1') ? 1 : 0;
-        }
-        if (pro) {  // fused GroupNorm + GELU prologue: the LDS-weight kernel with the per-channel affine table
-            const long nb = ((long)a.Hout * a.Wout + 127) / 128;
-            NPS_CHECK_ARG(nb < (1L << 31) && a.B < 65536, "conv2d_fwd: grid too large");
-            const int ncp = ((a.Cin + 31) / 32) * 32;
-            conv1x1_wl_kernel<6, 3, true><<<dim3((unsigned)nb, a.B), 256, 2 * 2 * 6 * 2048 + 6 * 32 * 4 + 2 * ncp * 4, s>>>(a, 1);
-            NPS_CHECK_LAUNCH("conv2d_fwd (split-fp16 1x1, LDS weights, GroupNorm prologue)");
-            return 0;
-        }
-        if (nps_launch_conv1x1_res(a, res_on, s)) return 0;  // resident weights (conv1x1_res.hip)
-        if (a.Cout <= 192 || g_x1_groups) {
-            // Cout > 192: channel groups of 192 (the input-gradient convs 192 -> 388 / 196), the ng groups of a pixel
-            // tile 8 work-groups apart (one XCD: the later groups read the tile from L2), tiles padded to 8
-            const int ng = (a.Cout + 191) / 192;
-            long nb = ((long)a.Hout * a.Wout + 127) / 128;
-            if (ng > 1) nb = (nb + 7) / 8 * 8 * ng;
-            NPS_CHECK_ARG(nb < (1L << 31) && a.B < 65536, "conv2d_fwd: grid too large");
-            // B-ring depth 3 (two stages of input in flight): 1x1 class 14.5 -> 14.0 ms per call over depth 2;
-            // depth 4 measured no faster, and spills the prologue kernel (profiles/x1_pipeline/steps.txt)
-            conv1x1_wl_kernel<6, 3><<<dim3((unsigned)nb, a.B), 256, 2 * 2 * 6 * 2048 + 6 * 32 * 4, s>>>(a, ng);
-            NPS_CHECK_LAUNCH("conv2d_fwd (split-fp16 1x1, LDS weights)");
-            return 0;
-        }
-        const int waves = ncob < 8 ? ncob : 8;
-        const long nblk = ((long)a.Hout * a.Wout + 63) / 64;
-        NPS_CHECK_ARG(nblk < (1L << 31) && a.B < 65536, "conv2d_fwd: grid too large");
-        const dim3 grid1((unsigned)nblk, a.B, (ncob + 7) / 8);
-        const int lds1 = lds_epi ? 64 * (64 * waves + 4) * 4 : 0;
-        conv1x1_x3_kernel<2, 2><<<grid1, 64 * waves, lds1, s>>>(a);
-        NPS_CHECK_LAUNCH("conv2d_fwd (split-fp16 1x1)");
-        return 0;
-    }
+    if (a.KH * a.KW == 1) return launch_conv1x1(a, pro, s);
     if (wide) {
         if (a.KH * a.KW == 9)
             pro ? launch_x3_one<9, 2, true, true>(a, grid, lds, s) : launch_x3_one<9, 2, false, true>(a, grid, lds, s);
@@ -1417,20 +1134,14 @@ extern "C" long nps_conv2d_x3_weight_span(const nps_conv2d_t* ap) {
     auto top = [&](long v) { span = v > span ? v : span; };
     if (nt == 1) {
         const long nst = (a.Cin + 2 * CK - 1) / (2 * CK);  // 32-channel stages: chunks 2 st, 2 st + 1
-        const char* e = getenv("NPS_X1_RES");
-        const int all = (e != nullptr && e[0] == '1') ? 1 : 0;
         int rncb = 0, rng = 0, rnres = 0;
-        const bool pro = a.gn_stats != nullptr || a.pre_act != 0;
-        if (!pro && nps_conv1x1_res_plan(a, all, &rncb, &rng, &rnres)) {
+        if (nps_conv1x1_res_plan(a, &rncb, &rng, &rnres)) {  // (never with a prologue: the plan refuses it)
             // conv1x1_res_kernel: chunks [0, nres), blocks [0, ng * NCB) (group grp at grp * NCB)
             top((rnres - 1) * gstride + (long)rng * rncb * 2048);
-        } else if (a.Cout <= 192 || g_x1_groups) {
+        } else {
             // conv1x1_wl_kernel<6, *>: wdma(min(st + 1, last)) -> chunks 2 last + 1, 6 blocks of the chunk at
             // its group's offset (ng groups of 6 blocks)
             top((2 * nst - 1) * gstride + (long)((a.Cout + 191) / 192) * 6 * 2048);
-        } else {
-            // conv1x1_x3_kernel: wave block min(cob, ncb / 2 - 1) x 2 blocks, chunks 2 st + k
-            top((2 * nst - 1) * gstride + ncb * 2048);
         }
     } else {
         const long nstages = (a.Cin + CK - 1) / CK;

@@ -158,20 +158,20 @@ __device__ __attribute__((aligned(64))) unsigned int c3d_zero16[16];
 // SIMPLE: one source covering the core frame at offset 0, channels a multiple of 16, no prologue (the
 // frame_pack3d output): a patch slot's address is fixed per tile (only the depth slice moves per stage), so
 // staging is one add + one 16-B load and one ds_write per slot
-// GLT (bf16 SIMPLE frames): the stage is copied global -> LDS by LDS-DMA (global_load_lds_dwordx4) instead of
+// DMA (bf16 SIMPLE frames): the stage is copied global -> LDS by LDS-DMA (global_load_lds_dwordx4) instead of
 // through registers; the lane-linear LDS image keeps the half-swap swizzle by swapping the SOURCE halves, and
-// slots outside the frame read a zero line — no staging registers, no commit pass
-// SB (with GLT): ONE stage buffer — load, barrier, compute, barrier — so a work-group needs half the LDS and three
-// fit a CU: each exposes its own load latency, the other two keep the MFMA pipe fed
-template <typename T, int K, int S, int TH, bool SIMPLE, bool GLT = false, bool SB = false>
+// slots outside the frame read a zero line — no staging registers, no commit pass.  It goes into ONE stage buffer
+// — load, barrier, compute, barrier — so a work-group needs half the LDS and three fit a CU: each exposes its own
+// load latency, the other two keep the MFMA pipe fed.  (LDS-DMA into two stage buffers measured no faster:
+// DESIGN.md, retired knobs.)
+template <typename T, int K, int S, int TH, bool SIMPLE, bool DMA = false>
 __device__ __forceinline__ void conv3d_body(const nps_conv3d_t& a, int nchunk, int ntile) {
     using G = Geo<K, S, TH>;
-    constexpr bool GL = GLT && SIMPLE && sizeof(T) == 2;
-    static_assert(!SB || GLT, "single stage buffer: LDS-DMA staging only");
+    static_assert(!DMA || (SIMPLE && sizeof(T) == 2), "LDS-DMA staging: packed bf16 frames only");
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
     T* ring = reinterpret_cast<T*>(smem);
     // [nchunk*16] GN affine per channel
-    float* gscale = reinterpret_cast<float*>(smem + (SB ? 1 : 2) * G::BUF * sizeof(T));
+    float* gscale = reinterpret_cast<float*>(smem + (DMA ? 1 : 2) * G::BUF * sizeof(T));
     float* gshift = gscale + nchunk * 16;
 
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
@@ -213,7 +213,7 @@ __device__ __forceinline__ void conv3d_body(const nps_conv3d_t& a, int nchunk, i
     const T* wbase = reinterpret_cast<const T*>(a.wpack) + (size_t)(z * ntile + tile) * K * nchunk * G::WTS;
     const int nstage = K * nchunk;
 
-    Vec8<T> pr[GL ? 1 : G::PPT], wr[GL ? 1 : G::WPT];
+    Vec8<T> pr[DMA ? 1 : G::PPT], wr[DMA ? 1 : G::WPT];
     // SIMPLE: per-slot element offset within a depth slice (-1: zero padding / past the patch)
     int soff[G::PPT];
     const T* sbase = reinterpret_cast<const T*>(a.src[0].ptr) + (size_t)b * a.Dc * a.Hc * a.Wc * a.Cin;
@@ -229,8 +229,8 @@ __device__ __forceinline__ void conv3d_body(const nps_conv3d_t& a, int nchunk, i
                 const int fh = h0 * S + prr, fw = w0 * S + pcc;
                 const int ch = fh < Hext ? ext_to_core(fh, a.Hc, a.circ, a.zpad) : -1;
                 const int cw = fw < Wext ? ext_to_core(fw, a.Wc, a.circ, a.zpad) : -1;
-                // (GL: the slot's LDS half holds channel half half ^ swz(pix), as commit's swizzled store)
-                if (ch >= 0 && cw >= 0) soff[i] = (ch * a.Wc + cw) * a.Cin + (GL ? (half ^ swz(pix)) : half) * 8;
+                // (DMA: the slot's LDS half holds channel half half ^ swz(pix), as commit's swizzled store)
+                if (ch >= 0 && cw >= 0) soff[i] = (ch * a.Wc + cw) * a.Cin + (DMA ? (half ^ swz(pix)) : half) * 8;
             }
         }
     }
@@ -305,13 +305,13 @@ __device__ __forceinline__ void conv3d_body(const nps_conv3d_t& a, int nchunk, i
         }
     };
 
-    // GL: stage st -> ring buffer buf by LDS-DMA; wave w's instruction i fills slots [256 i + 64 w, + 64)
-    auto fetch_gl = [&](int st, int buf) {
-        if constexpr (GL) {
+    // DMA: stage st -> the stage buffer by LDS-DMA; wave w's instruction i fills slots [256 i + 64 w, + 64)
+    auto fetch_gl = [&](int st) {
+        if constexpr (DMA) {
             const int kd = st / nchunk, chunk = st - kd * nchunk;
             const int cd = ext_to_core(md * S + kd, a.Dc, a.circ, a.zpad);
             const T* sp = sbase + (size_t)(cd < 0 ? 0 : cd) * slice + chunk * 16;
-            T* P = ring + buf * G::BUF;
+            T* P = ring;
 #pragma unroll
             for (int i = 0; i < G::PPT; ++i) {
                 const int idx = tid + 256 * i;
@@ -344,8 +344,8 @@ __device__ __forceinline__ void conv3d_body(const nps_conv3d_t& a, int nchunk, i
 #pragma unroll
             for (int q = 0; q < 16; ++q) acc[cb][r][q] = 0.f;
 
-    if constexpr (GL) {
-        fetch_gl(0, 0);
+    if constexpr (DMA) {
+        fetch_gl(0);
         asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
     } else {
         fetch(0);
@@ -354,13 +354,9 @@ __device__ __forceinline__ void conv3d_body(const nps_conv3d_t& a, int nchunk, i
     __syncthreads();
     const int col = lane & 31, hl = lane >> 5;
     for (int st = 0; st < nstage; ++st) {
-        const int buf = SB ? 0 : (st & 1);
-        if constexpr (SB) {
-        } else if constexpr (GL) {
-            if (st + 1 < nstage) fetch_gl(st + 1, buf ^ 1);
-        } else {
+        const int buf = DMA ? 0 : (st & 1);
+        if constexpr (!DMA)
             if (st + 1 < nstage) fetch(st + 1);
-        }
         const T* P = ring + buf * G::BUF;
         const T* Wl = P + G::PATCH;
 #pragma unroll
@@ -409,14 +405,12 @@ __device__ __forceinline__ void conv3d_body(const nps_conv3d_t& a, int nchunk, i
                 }
             }
         }
-        if constexpr (SB) {
+        if constexpr (DMA) {
             if (st + 1 < nstage) {
                 __syncthreads();  // every read of the buffer is done
-                fetch_gl(st + 1, 0);
+                fetch_gl(st + 1);
                 asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
             }
-        } else if constexpr (GL) {
-            asm volatile("s_waitcnt vmcnt(0)" ::: "memory");  // this wave's DMA of stage st + 1 has landed
         } else {
             if (st + 1 < nstage) commit(st + 1, buf ^ 1);
         }
@@ -548,27 +542,26 @@ __device__ __forceinline__ void conv3d_body(const nps_conv3d_t& a, int nchunk, i
     }
 }
 
-template <typename T, int K, int S, int TH, bool SIMPLE, bool GLT = false, bool SB = false>
+// The four shipped forms of conv3d_body (dispatch): how a stage reaches LDS, and the occupancy the kernel is held to.
+enum class Form {
+    REG,     // register-staged, two stage buffers
+    REG_O4,  // the same held to four waves per SIMD: the 1x1x1 over several sources, a streaming kernel
+    DMA,     // LDS-DMA into one stage buffer
+    DMA_O4,  // the same held to four waves per SIMD — four work-groups per CU
+};
+template <typename T, int K, int S, int TH, bool SIMPLE, bool DMA = false>
 __global__ __launch_bounds__(256) void conv3d_kernel(const nps_conv3d_t a, int nchunk, int ntile) {
-    conv3d_body<T, K, S, TH, SIMPLE, GLT, SB>(a, nchunk, ntile);
+    conv3d_body<T, K, S, TH, SIMPLE, DMA>(a, nchunk, ntile);
 }
-// (dev variant: the same body held to two waves per SIMD, for register-heavy tile shapes)
-template <typename T, int K, int S, int TH, bool SIMPLE, bool GLT = false>
-__global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2))) void conv3d_kernel_o2(const nps_conv3d_t a,
-                                                                                             int nchunk, int ntile) {
-    conv3d_body<T, K, S, TH, SIMPLE, GLT>(a, nchunk, ntile);
-}
-// (register-staged, held to four waves per SIMD: the 1x1x1 over several sources, a streaming kernel)
 template <typename T, int K, int S, int TH, bool SIMPLE>
 __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(4))) void conv3d_kernel_o4r(const nps_conv3d_t a,
                                                                                               int nchunk, int ntile) {
     conv3d_body<T, K, S, TH, SIMPLE>(a, nchunk, ntile);
 }
-// (one stage buffer held to four waves per SIMD — four work-groups per CU)
 template <typename T, int K, int S, int TH, bool SIMPLE>
 __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(4))) void conv3d_kernel_o4(const nps_conv3d_t a,
                                                                                              int nchunk, int ntile) {
-    conv3d_body<T, K, S, TH, SIMPLE, true, true>(a, nchunk, ntile);
+    conv3d_body<T, K, S, TH, SIMPLE, true>(a, nchunk, ntile);
 }
 
 // wpack[(((((z*ntile + tile)*K + kd)*nchunk + chunk)*K*K + tap)*64 + col)*16 + k]
@@ -1175,15 +1168,6 @@ __global__ __launch_bounds__(256) void conv3d_1x1_kernel(const nps_conv3d_t a, i
     }
 }
 
-// dev knob NPS_C3D_1X1=0: 1x1x1 bf16 convs on conv3d_kernel (A/B)
-bool c3d_1x1_on() {
-    static const int g = [] {
-        const char* e = std::getenv("NPS_C3D_1X1");
-        return (e != nullptr && e[0] == '0') ? 0 : 1;
-    }();
-    return g != 0;
-}
-
 bool c3d_1x1_eligible(const nps_conv3d_t& a) {
     if (!a.bf16 || a.K != 1 || a.stride != 1 || a.transposed || a.circ != 0 || a.zpad != 0) return false;
     if (a.Cout > 128 || a.Cin > 256 || (a.Cout & 3) != 0 || (a.out_C & 3) != 0) return false;
@@ -1192,8 +1176,7 @@ bool c3d_1x1_eligible(const nps_conv3d_t& a) {
     // (three-source frames, the up-path cat(h, skip, vb): measured slower than conv3d_kernel — 437 vs 360 us at
     // 132 -> 64 over 16 x 128^2, B = 8, double-buffered; 538 vs 363 single-buffered at 4 waves per SIMD; C5 -2 %,
     // profiles/r6/experiments/c5_1x1x1_three_source_ab.txt; two sources and GN-prologue frames gain)
-    if (a.nsrc > 2) return false;
-    return c3d_1x1_on();
+    return a.nsrc <= 2;
 }
 
 template <int NCB, int NCH, bool PRO>
@@ -1201,6 +1184,12 @@ int launch_1x1(const nps_conv3d_t& a, int nchunk, hipStream_t s) {
     const size_t lds = (size_t)nchunk * NCB * 32 * 32 + NCB * 32 * sizeof(float) + 2 * (size_t)nchunk * 16 * sizeof(float) +
                        8 * sizeof(double);
     NPS_CHECK_ARG(lds <= 160 * 1024, "conv3d (1x1x1): %zu B of LDS", lds);
+    static bool attr = false;  // (NCB = 4 with 16 chunks takes 68 160 B: past the 64 KiB a kernel gets unasked)
+    if (!attr) {
+        (void)hipFuncSetAttribute((const void*)conv3d_1x1_kernel<NCB, NCH, PRO>,
+                                  hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
+        attr = true;
+    }
     const long nvox = (long)a.Dc * a.Hc * a.Wc;
     NPS_CHECK_ARG(nvox < (1L << 31) - 32, "conv3d (1x1x1): volume too large");
     const long ntv = (nvox + 31) / 32;
@@ -1234,15 +1223,17 @@ int dispatch_1x1(const nps_conv3d_t& a, int nchunk, hipStream_t s) {
     return w4 ? launch_1x1<4, 16, PRO>(a, nchunk, s) : launch_1x1<2, 16, PRO>(a, nchunk, s);
 }
 
-template <typename T, int K, int S, int TH, bool SIMPLE, bool O2 = false, bool GLT = false, bool SB = false,
-          bool O4R = false>
+template <typename T, int K, int S, int TH, bool SIMPLE, Form F = Form::REG>
 int launch(const nps_conv3d_t& a, int nchunk, int ntile, hipStream_t s) {
-    auto kern = conv3d_kernel<T, K, S, TH, SIMPLE, GLT, SB>;
-    if constexpr (O4R) kern = conv3d_kernel_o4r<T, K, S, TH, SIMPLE>;
-    if constexpr (O2 && SB) kern = conv3d_kernel_o4<T, K, S, TH, SIMPLE>;
-    if constexpr (O2 && !SB) kern = conv3d_kernel_o2<T, K, S, TH, SIMPLE, GLT>;
+    constexpr bool dma = F == Form::DMA || F == Form::DMA_O4;  // one stage buffer
+    const auto kern = [] {  // (if constexpr: only the chosen kernel is instantiated)
+        if constexpr (F == Form::REG) return conv3d_kernel<T, K, S, TH, SIMPLE>;
+        else if constexpr (F == Form::REG_O4) return conv3d_kernel_o4r<T, K, S, TH, SIMPLE>;
+        else if constexpr (F == Form::DMA) return conv3d_kernel<T, K, S, TH, SIMPLE, true>;
+        else return conv3d_kernel_o4<T, K, S, TH, SIMPLE>;
+    }();
     using G = Geo<K, S, TH>;
-    const size_t lds = (SB ? 1 : 2) * (size_t)G::BUF * sizeof(T) + 2 * (size_t)nchunk * 16 * sizeof(float);
+    const size_t lds = (dma ? 1 : 2) * (size_t)G::BUF * sizeof(T) + 2 * (size_t)nchunk * 16 * sizeof(float);
     NPS_CHECK_ARG(lds <= 160 * 1024, "conv3d: %zu B of LDS (Cin too large for the GroupNorm table)", lds);
     static bool attr = false;
     if (!attr) {
@@ -1267,31 +1258,15 @@ bool simple_frame(const nps_conv3d_t& a) {
 template <typename T>
 int dispatch(const nps_conv3d_t& a, int nchunk, int ntile, hipStream_t s) {
     const bool sim = simple_frame(a);
-    // bf16 fast-path frames: stage copies by LDS-DMA into ONE stage buffer (SB) — three work-groups per CU (3x3x3),
-    // four for the register-light 2x2x2 phases (held to 4 waves per SIMD); NPS_C3D_GLDS=0: the register-staged
-    // double-buffered kernels.  Dev knob NPS_C3D_TH16 (3x3x3 stride 1, measured no faster, records in
-    // profiles/r6/experiments/c5_conv3d_glds_ab.txt): 1 / 2 / 3 / 5 16-row tiles (2: two waves per SIMD, 3: LDS-DMA,
-    // 5: both), 4 8-row LDS-DMA with two stage buffers, 7 the one-buffer kernel held to 4 waves per SIMD
-    static int th16 = -1, glds = 1;
-    if (th16 < 0) {
-        const char* e = std::getenv("NPS_C3D_TH16");
-        th16 = (e != nullptr && e[0] >= '1' && e[0] <= '7' && e[0] != '6') ? e[0] - '0' : 0;
-        const char* g = std::getenv("NPS_C3D_GLDS");
-        glds = (g != nullptr && g[0] == '0') ? 0 : 1;
-    }
+    // bf16 fast-path frames: stage copies by LDS-DMA into one stage buffer — three work-groups per CU (3x3x3), four
+    // for the register-light 2x2x2 phases (held to 4 waves per SIMD).  NPS_C3D_GLDS=0 (test-only):
+    // the register-staged double-buffered kernels these replaced, which the tests pin them against bit for bit.
+    static const bool glds = nps::env_flag("NPS_C3D_GLDS", true);
     if constexpr (sizeof(T) == 2)
         if (sim && glds) {
-            if (a.K == 3 && a.stride == 1) {
-                if (th16 == 1) return launch<T, 3, 1, 16, true>(a, nchunk, ntile, s);
-                if (th16 == 2) return launch<T, 3, 1, 16, true, true>(a, nchunk, ntile, s);
-                if (th16 == 3) return launch<T, 3, 1, 16, true, false, true>(a, nchunk, ntile, s);
-                if (th16 == 4) return launch<T, 3, 1, 8, true, false, true>(a, nchunk, ntile, s);
-                if (th16 == 5) return launch<T, 3, 1, 16, true, true, true>(a, nchunk, ntile, s);
-                if (th16 == 7) return launch<T, 3, 1, 8, true, true, true, true>(a, nchunk, ntile, s);
-                return launch<T, 3, 1, 8, true, false, true, true>(a, nchunk, ntile, s);
-            }
-            if (a.K == 3 && a.stride == 2) return launch<T, 3, 2, 4, true, false, true, true>(a, nchunk, ntile, s);
-            if (a.K == 2 && a.stride == 1) return launch<T, 2, 1, 8, true, true, true, true>(a, nchunk, ntile, s);
+            if (a.K == 3 && a.stride == 1) return launch<T, 3, 1, 8, true, Form::DMA>(a, nchunk, ntile, s);
+            if (a.K == 3 && a.stride == 2) return launch<T, 3, 2, 4, true, Form::DMA>(a, nchunk, ntile, s);
+            if (a.K == 2 && a.stride == 1) return launch<T, 2, 1, 8, true, Form::DMA_O4>(a, nchunk, ntile, s);
         }
     if (a.K == 3 && a.stride == 1)
         return sim ? launch<T, 3, 1, 8, true>(a, nchunk, ntile, s) : launch<T, 3, 1, 8, false>(a, nchunk, ntile, s);
@@ -1302,14 +1277,10 @@ int dispatch(const nps_conv3d_t& a, int nchunk, int ntile, hipStream_t s) {
     if (a.K == 1 && a.stride == 1) {
         // bf16 multi-source 1x1x1 (the C5 shortcuts over cat(h, skip, vb)): a streaming kernel, held to four waves
         // per SIMD (four work-groups per CU, 128 VGPRs): (64, 64, 4) -> 64 at 16x128^2 471 -> 385 us, bit-identical
-        // (profiles/r6/experiments/c5_conv3d_glds_ab.txt); NPS_C3D_K1O4=0: three work-groups
-        static int k1 = -1;
-        if (k1 < 0) {
-            const char* e = std::getenv("NPS_C3D_K1O4");
-            k1 = (e != nullptr && e[0] == '0') ? 0 : 1;
-        }
+        // (profiles/r6/experiments/c5_conv3d_glds_ab.txt); NPS_C3D_K1O4=0 (test-only): three work-groups
+        static const bool k1o4 = nps::env_flag("NPS_C3D_K1O4", true);
         if constexpr (sizeof(T) == 2)
-            if (!sim && k1) return launch<T, 1, 1, 8, false, false, false, false, true>(a, nchunk, ntile, s);
+            if (!sim && k1o4) return launch<T, 1, 1, 8, false, Form::REG_O4>(a, nchunk, ntile, s);
         return sim ? launch<T, 1, 1, 8, true>(a, nchunk, ntile, s) : launch<T, 1, 1, 8, false>(a, nchunk, ntile, s);
     }
     NPS_CHECK_ARG(false, "conv3d: K=%d stride=%d not supported (K in {1,2,3}, stride 2 only for K=3)", a.K, a.stride);
@@ -1393,15 +1364,9 @@ extern "C" int nps_frame_pack3d(const nps_conv3d_t* ap, void* out, int Cpad, voi
     const long nb = (nitem + 2047) / 2048 < 1024 ? (nitem + 2047) / 2048 : 1024;
     hipStream_t s = (hipStream_t)stream;
     const dim3 grid((unsigned)(nb > 0 ? nb : 1), (unsigned)a.B);
-    static int mflat_off = -1;  // dev knob NPS_PACK3D_MFLAT=0: multi-source frames through the general decode
-    static int flat_on = 1;     // NPS_PACK3D_FLAT=0: offset-0 frames on frame_pack3d_kernel instead of the flat kernel
-    if (mflat_off < 0) {
-        const char* e = std::getenv("NPS_PACK3D_MFLAT");
-        mflat_off = (e != nullptr && e[0] == '0') ? 1 : 0;
-        const char* f = std::getenv("NPS_PACK3D_FLAT");
-        flat_on = (f != nullptr && f[0] == '0') ? 0 : 1;
-    }
-    bool flat = flat_on && mflat_off == 0;
+    // NPS_PACK3D_MFLAT=0 (test-only): every frame through frame_pack3d_kernel's general decode
+    static const bool mflat = nps::env_flag("NPS_PACK3D_MFLAT", true);
+    bool flat = mflat;
     for (int i = 0; i < a.nsrc; ++i) {
         const nps_src3_t& q = a.src[i];
         flat = flat && q.off_d == 0 && q.off_h == 0 && q.off_w == 0 && q.D == a.Dc && q.H == a.Hc && q.W == a.Wc &&
@@ -1419,9 +1384,9 @@ extern "C" int nps_frame_pack3d(const nps_conv3d_t* ap, void* out, int Cpad, voi
         return 0;
     }
     if (a.bf16)
-        frame_pack3d_kernel<bf16_t><<<grid, 256, 0, s>>>(a, reinterpret_cast<bf16_t*>(out), Cpad, mflat_off != 0);
+        frame_pack3d_kernel<bf16_t><<<grid, 256, 0, s>>>(a, reinterpret_cast<bf16_t*>(out), Cpad, !mflat);
     else
-        frame_pack3d_kernel<float><<<grid, 256, 0, s>>>(a, reinterpret_cast<float*>(out), Cpad, mflat_off != 0);
+        frame_pack3d_kernel<float><<<grid, 256, 0, s>>>(a, reinterpret_cast<float*>(out), Cpad, !mflat);
     NPS_CHECK_LAUNCH("frame_pack3d");
     return 0;
 }

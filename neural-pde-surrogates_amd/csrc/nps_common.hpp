@@ -4,6 +4,7 @@
 #include <cstdio>
 #include <cstdarg>
 #include <cmath>
+#include <cstdlib>
 
 #include "../../include/nps.h"
 
@@ -13,6 +14,15 @@ typedef float f32x16 __attribute__((ext_vector_type(16)));
 namespace nps {
 
 void set_error(const char* fmt, ...);
+
+// The library's only reader of the environment: a boolean switch, off when the variable starts with '0', on when
+// it starts with '1', dflt otherwise.  Call sites keep the result in a static, so each is read once per process.
+// Every name passed here is listed in INTEGRATION.md (tests/test_knob_list.py compares the two sets).
+inline bool env_flag(const char* name, bool dflt) {
+    const char* e = std::getenv(name);
+    if (e == nullptr || (e[0] != '0' && e[0] != '1')) return dflt;
+    return e[0] == '1';
+}
 
 #define NPS_CHECK_ARG(cond, ...)            \
     do {                                    \

@@ -280,7 +280,8 @@ __global__ void transpose_kernel(const float* __restrict__ in, float* __restrict
 //   ws[block][w1 | b1 | w2 | b2]  per-block parameter-gradient partials (summed by nps_channel_sums).
 // NC_ > 0: the loop bounds (num_c, tw and the derived kernel sizes) are compile-time, so the inner
 // reductions unroll (their LDS reads issue back to back instead of one latency per FMA) and the weights
-// become scalar loads; NC_ == 0 is the generic form (the arguments decide).
+// become scalar loads; NC_ == 0 is the generic form (the arguments decide).  Only <0, 0> is instantiated: the
+// twophase shapes (num_c 1 / 3, tw 25) run on timeconv_bwd_fast_kernel below.
 template <int NC_, int TW_>
 __global__ __launch_bounds__(64) void timeconv_bwd_kernel(
     const float* __restrict__ pre, const float* __restrict__ u, const float* __restrict__ w1,
@@ -920,15 +921,6 @@ int tc_bwd_blocks() {
     }
     return n;
 }
-
-// NPS_TC_BWD_GENERIC=1 routes every shape through the one-wave generic kernel (A/B and parity checks)
-bool tc_bwd_generic() {
-    static const int g = [] {
-        const char* e = std::getenv("NPS_TC_BWD_GENERIC");
-        return e && e[0] == '1' ? 1 : 0;
-    }();
-    return g != 0;
-}
 }  // namespace
 
 extern "C" int nps_timeconv_decode_bwd(const float* pre, const float* u, const float* w1, const float* b1,
@@ -949,16 +941,12 @@ extern "C" int nps_timeconv_decode_bwd(const float* pre, const float* u, const f
     if (!attr_set) {
         (void)hipFuncSetAttribute((const void*)timeconv_bwd_kernel<0, 0>, hipFuncAttributeMaxDynamicSharedMemorySize,
                                   160 * 1024);
-        (void)hipFuncSetAttribute((const void*)timeconv_bwd_kernel<3, 25>, hipFuncAttributeMaxDynamicSharedMemorySize,
-                                  160 * 1024);
-        (void)hipFuncSetAttribute((const void*)timeconv_bwd_kernel<1, 25>, hipFuncAttributeMaxDynamicSharedMemorySize,
-                                  160 * 1024);
         attr_set = true;
     }
     const int HW = H * W;
     const dim3 grid((HW + 63) / 64, B);
     hipStream_t s = (hipStream_t)stream;
-    if ((num_c == 3 || num_c == 1) && tw == 25 && !tc_bwd_generic()) {  // the twophase cfgs
+    if ((num_c == 3 || num_c == 1) && tw == 25) {  // the twophase cfgs
         constexpr int PX = 16;
         const int ngroups = B * ((HW + PX - 1) / PX);
         const int nrows = B * ((HW + 63) / 64);
@@ -970,13 +958,7 @@ extern "C" int nps_timeconv_decode_bwd(const float* pre, const float* u, const f
         else
             timeconv_bwd_fast_kernel<1, 25, PX><<<G, 256, tc_bwd_lds<1, 25, PX>(), s>>>(
                 pre, u, w1, b1, w2, b2, dtcum, mask, mask_S, mask_ch, gout, gpre, ws, HW, ngroups, nrows, act_tanh);
-    } else if (num_c == 3 && tw == 25)
-        timeconv_bwd_kernel<3, 25><<<grid, 64, lds, s>>>(pre, u, w1, b1, w2, b2, dtcum, mask, mask_S, mask_ch, gout,
-                                                         gpre, ws, num_c, tw, HW, ka, kb, L1, act_tanh, nparams);
-    else if (num_c == 1 && tw == 25)
-        timeconv_bwd_kernel<1, 25><<<grid, 64, lds, s>>>(pre, u, w1, b1, w2, b2, dtcum, mask, mask_S, mask_ch, gout,
-                                                         gpre, ws, num_c, tw, HW, ka, kb, L1, act_tanh, nparams);
-    else
+    } else  // every other shape: the one-wave generic kernel
         timeconv_bwd_kernel<0, 0><<<grid, 64, lds, s>>>(pre, u, w1, b1, w2, b2, dtcum, mask, mask_S, mask_ch, gout,
                                                         gpre, ws, num_c, tw, HW, ka, kb, L1, act_tanh, nparams);
     NPS_CHECK_LAUNCH("timeconv_decode_bwd");

@@ -831,14 +831,9 @@ size_t idft_w_lds(int m2, int W) {
 template <typename TIn = float>
 void launch_dft_w(dim3 grid, int bs, size_t lds, hipStream_t s, const nps_conv2d_t& a, int m2, float2* X1, float scale,
                   int c2r_adj) {
-    static int mfma = -1;  // dev knob NPS_DFTW_MFMA=0: the VALU W-pass
-    if (mfma < 0) {
-        const char* e = getenv("NPS_DFTW_MFMA");
-        mfma = (e != nullptr && e[0] == '0') ? 0 : 1;
-    }
     bool quads = true;  // every source 4-channel aligned: a lane's 16-B quad lies in one source
     for (int i = 0; i < a.nsrc; ++i) quads = quads && (a.src[i].C & 3) == 0;
-    if (std::is_same<TIn, float>::value && mfma && quads && m2 <= 16 && (a.Win & 1) == 0 &&
+    if (std::is_same<TIn, float>::value && quads && m2 <= 16 && (a.Win & 1) == 0 &&
         a.Win * 32 * 4 <= 64 * 1024) {
         static int ncu = 0;
         if (ncu == 0) {
@@ -962,15 +957,17 @@ extern "C" int nps_spectral_pack_weights(const float* w1, const float* w2, float
     return 0;
 }
 
+// NPS_MIX_VALU=1: the scalar-FMA mixer and its backward instead of the MFMA kernels
+static bool mix_valu() {
+    static const bool on = nps::env_flag("NPS_MIX_VALU", false);
+    return on;
+}
+
 extern "C" int nps_spectral_mix(const float* X2, const float* wpack, float* Y, int B, int R, int m2, int Cin, int Cout,
                                 void* stream) {
     NPS_CHECK_ARG(X2 && wpack && Y && B > 0 && R > 0 && m2 > 0 && Cin > 0 && Cout > 0, "spectral_mix: bad args");
     hipStream_t s = (hipStream_t)stream;
-    static int use_valu = -1;  // dev knob NPS_MIX_VALU=1: the scalar-FMA mixer (A/B reference)
-    if (use_valu < 0) {
-        const char* e = getenv("NPS_MIX_VALU");
-        use_valu = (e != nullptr && e[0] == '1') ? 1 : 0;
-    }
+    const bool use_valu = mix_valu();  // the scalar-FMA mixer (A/B reference)
     const int nmodes = R * m2;
     if (!use_valu && (Cout & 3) == 0) {
         const dim3 grid(nmodes, (Cout + MIX_OC - 1) / MIX_OC);
@@ -1141,11 +1138,7 @@ extern "C" int nps_spectral_mix_bwd(const float* X2, const float* wpack, const f
                                     int B, int R, int m2, int Cin, int Cout, void* stream) {
     NPS_CHECK_ARG(X2 && wpack && gY && gX2 && gwpack && B > 0 && R > 0 && m2 > 0 && Cin > 0 && Cout > 0,
                   "spectral_mix_bwd: bad args");
-    static int use_valu = -1;  // dev knob NPS_MIX_VALU=1: the scalar-FMA backward (A/B reference)
-    if (use_valu < 0) {
-        const char* e = getenv("NPS_MIX_VALU");
-        use_valu = (e != nullptr && e[0] == '1') ? 1 : 0;
-    }
+    const bool use_valu = mix_valu();  // the scalar-FMA backward (A/B reference)
     if (!use_valu && (Cout & 3) == 0 && B <= 32) {
         const dim3 grid(R * m2, (Cin + 63) / 64);
         const auto* x = reinterpret_cast<const float2*>(X2);

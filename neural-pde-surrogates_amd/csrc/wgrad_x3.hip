@@ -740,11 +740,26 @@ __global__ void wgrad_fold_kernel(const float* __restrict__ w, float* __restrict
 // profiles/r6/experiments/train_b2_knob_sweep.jsonl; 1024 and a larger minimum split were slower)
 inline long wx_wgs(const nps_wgrad_t& p) { return (long)p.B * p.Ha * p.Wa <= 200000 ? 256 : 512; }
 constexpr long WX_MINT = 8;  // minimum pixel tiles per split
-// dev knob NPS_WX_REMAP=0: the plain (tile-fastest) work-group order
-const int g_wx_remap = [] {
-    const char* e = std::getenv("NPS_WX_REMAP");
-    return (e != nullptr && e[0] == '0') ? 0 : 1;
-}();
+
+// Split K (the ntiles pixel tiles) of a launcher whose grid is base (M x N tiles) x splits work-groups: at most
+// wx_wgs / base splits (a grid just past a multiple of 256 would add a nearly empty round), >= WX_MINT tiles each,
+// `per` tiles per split.  A count that is a multiple of 8 (16 and more are rounded down to one) runs the kernels'
+// XCD-aware tile order (remap, kernel comment); any other the plain tile-fastest order, with only the splits that own tiles.
+struct WxSplit {
+    long splits;
+    int per, remap;
+};
+inline WxSplit wx_split(long ntiles, long base, const nps_wgrad_t& p) {
+    long splits = wx_wgs(p) / base;
+    const long max_splits = (ntiles + WX_MINT - 1) / WX_MINT;
+    if (splits > max_splits) splits = max_splits;
+    if (splits >= 16) splits &= ~7L;
+    if (splits < 1) splits = 1;
+    const int per = (int)((ntiles + splits - 1) / splits);
+    const int remap = splits % 8 == 0 ? 1 : 0;
+    if (!remap) splits = (ntiles + per - 1) / per;  // (the rest would exit at once)
+    return {splits, per, remap};
+}
 
 template <int KH, int KW>
 int launch_wgrad_x3(const nps_wgrad_t& p, const float* ar, const float* xr, float* ws, hipStream_t s,
@@ -754,17 +769,7 @@ int launch_wgrad_x3(const nps_wgrad_t& p, const float* ar, const float* xr, floa
     NPS_CHECK_ARG(ntiles < (1L << 30), "conv2d_wgrad_x3: too many tiles");
     const int n_mt = (p.M + 63) / 64, n_nt = (p.N + 63) / 64;
     const long base = (long)n_mt * n_nt;
-    // split K (pixel tiles): at most 2 work-groups in turn per CU (the first one's atomics overlap the
-    // second one's tiles; a grid just past a multiple of 256 would add a nearly empty round), >= 8 tiles each
-    long splits = wx_wgs(p) / base;
-    const long max_splits = (ntiles + WX_MINT - 1) / WX_MINT;
-    if (splits > max_splits) splits = max_splits;
-    if (splits >= 16) splits &= ~7L;  // a multiple of 8: the XCD-aware tile order (kernel comment)
-    if (splits < 1) splits = 1;
-    const int per = (int)((ntiles + splits - 1) / splits);
-    const long used = (ntiles + per - 1) / per;  // splits that own tiles (the rest exit at once)
-    const int remap = (splits % 8 == 0 && g_wx_remap) ? 1 : 0;
-    if (!remap) splits = used;
+    const auto [splits, per, remap] = wx_split(ntiles, base, p);
     NPS_CHECK_ARG(base * splits < (1L << 31), "conv2d_wgrad_x3: grid too large");
     const size_t lds = wx_lds_bytes(KH);
     static bool attr_set = false;
@@ -797,15 +802,7 @@ int launch_wgrad1_wide(const nps_wgrad_t& p, const float* ar, const float* xr, f
     NPS_CHECK_ARG(ntiles < (1L << 30), "conv2d_wgrad_x3 (1x1): too many tiles");
     const int n_mt = (p.M + W1_ROWS - 1) / W1_ROWS, n_nt = (p.N + W1_ROWS - 1) / W1_ROWS;
     const long base = (long)n_mt * n_nt;
-    long splits = wx_wgs(p) / base;  // two work-groups per CU in turn (LDS: 120 KiB each, one resident)
-    const long max_splits = (ntiles + WX_MINT - 1) / WX_MINT;
-    if (splits > max_splits) splits = max_splits;
-    if (splits >= 16) splits &= ~7L;
-    if (splits < 1) splits = 1;
-    const int per = (int)((ntiles + splits - 1) / splits);
-    const long used = (ntiles + per - 1) / per;
-    const int remap = (splits % 8 == 0 && g_wx_remap) ? 1 : 0;
-    if (!remap) splits = used;
+    const auto [splits, per, remap] = wx_split(ntiles, base, p);
     NPS_CHECK_ARG(base * splits < (1L << 31), "conv2d_wgrad_x3 (1x1): grid too large");
     static bool attr_set = false;
     if (!attr_set) {
@@ -836,15 +833,7 @@ int launch_wgrad2_wide(const nps_wgrad_t& p, const float* ar, const float* xr, f
     NPS_CHECK_ARG(ntiles < (1L << 30), "conv2d_wgrad_x3 (2x2): too many tiles");
     const int n_mt = (p.M + W2_ROWS - 1) / W2_ROWS, n_nt = (p.N + W2_ROWS - 1) / W2_ROWS;
     const long base = (long)n_mt * n_nt;
-    long splits = wx_wgs(p) / base;
-    const long max_splits = (ntiles + WX_MINT - 1) / WX_MINT;
-    if (splits > max_splits) splits = max_splits;
-    if (splits >= 16) splits &= ~7L;
-    if (splits < 1) splits = 1;
-    const int per = (int)((ntiles + splits - 1) / splits);
-    const long used = (ntiles + per - 1) / per;
-    const int remap = (splits % 8 == 0 && g_wx_remap) ? 1 : 0;
-    if (!remap) splits = used;
+    const auto [splits, per, remap] = wx_split(ntiles, base, p);
     NPS_CHECK_ARG(base * splits < (1L << 31), "conv2d_wgrad_x3 (2x2): grid too large");
     static bool attr_set = false;
     if (!attr_set) {
@@ -867,17 +856,6 @@ int launch_wgrad2_wide(const nps_wgrad_t& p, const float* ar, const float* xr, f
     return 0;
 }
 
-// dev knob NPS_WX_WIDE1=0: 1x1 weight gradients on the 64 x 64 tiles of wgrad_x3_kernel
-const int g_wx_wide1 = [] {
-    const char* e = std::getenv("NPS_WX_WIDE1");
-    return (e != nullptr && e[0] == '0') ? 0 : 1;
-}();
-// dev knob NPS_WX_WIDE2=0: 2x2 weight gradients on the 64 x 64 tiles of wgrad_x3_kernel
-const int g_wx_wide2 = [] {
-    const char* e = std::getenv("NPS_WX_WIDE2");
-    return (e != nullptr && e[0] == '0') ? 0 : 1;
-}();
-
 }  // namespace
 
 // partials [KH*KW][M][N] + the bias row [M] (nps_wgrad_t.db)
@@ -898,12 +876,12 @@ int wgrad_x3_dispatch(const nps_wgrad_t* pp, const float* a_range, const float* 
     hipStream_t s = (hipStream_t)stream;
     switch (p.KH) {
         case 1:
-            if (g_wx_wide1 && p.pad_y == 0 && p.pad_x == 0 && p.circ == 0 && p.Ha == p.Hx && p.Wa == p.Wx)
+            if (p.pad_y == 0 && p.pad_x == 0 && p.circ == 0 && p.Ha == p.Hx && p.Wa == p.Wx)
                 return launch_wgrad1_wide(p, a_range, x_range, ws, s, acc);
             return launch_wgrad_x3<1, 1>(p, a_range, x_range, ws, s, acc);
         case 2:
             // (the wide kernel needs M, N > 64 to beat the 64 x 64 tiles)
-            if (g_wx_wide2 && p.M > 64 && p.N > 64) return launch_wgrad2_wide(p, a_range, x_range, ws, s, acc);
+            if (p.M > 64 && p.N > 64) return launch_wgrad2_wide(p, a_range, x_range, ws, s, acc);
             return launch_wgrad_x3<2, 2>(p, a_range, x_range, ws, s, acc);
         default: return launch_wgrad_x3<3, 3>(p, a_range, x_range, ws, s, acc);
     }

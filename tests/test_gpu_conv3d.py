@@ -251,18 +251,24 @@ def test_conv3d_out_stats_with_accumulate_addend_act_and_phases(dt):
     torch.testing.assert_close(carried(st), passes(u), rtol=1e-5, atol=1e-2)
 
 
-@pytest.mark.parametrize("cout", [64, 96, 128])
-@pytest.mark.parametrize("chans,offs", [((64, 4), ((0, 0, 0), (0, 0, 0))),
-                                        ((64, 64, 4), ((0, 0, 0), (-1, 1, 0), (1, 0, 0))),
-                                        ((192, 8), ((0, 0, 0), (0, -2, 1)))])
-def test_conv3d_1x1x1_bf16_streaming(cout, chans, offs):
+_STREAM_FRAMES = [((64, 4), ((0, 0, 0), (0, 0, 0))),
+                  ((64, 64, 4), ((0, 0, 0), (-1, 1, 0), (1, 0, 0))),
+                  ((192, 8), ((0, 0, 0), (0, -2, 1)))]
+_STREAM_CASES = [pytest.param(cout, chans, offs, 2, (5, 9, 37), id=f"chans{i}-offs{i}-{cout}")
+                 for i, (chans, offs) in enumerate(_STREAM_FRAMES) for cout in (64, 96, 128)]
+# 16 K-steps x 4 channel blocks: 68 160 B of LDS, past the 64 KiB a kernel gets without asking for more
+_STREAM_CASES.append(pytest.param(128, (256,), ((0, 0, 0),), 1, (4, 16, 32), id="cin256-128"))
+
+
+@pytest.mark.parametrize("cout,chans,offs,B,dhw", _STREAM_CASES)
+def test_conv3d_1x1x1_bf16_streaming(cout, chans, offs, B, dhw):
     """The bf16 1x1x1 kernel (conv3d_1x1_kernel: weights resident in LDS, every K-step's load of a 32-voxel tile in
     flight at once): the ResidualBlock shortcut over cat(h, crop_Nd(skip), crop_Nd(vb)) at Cin 68 / 132 / 200 (5, 9
     and 16 K-step register sets), Cout 64 / 96 / 128 (2 and 4 channel blocks), a volume that is not a multiple of
-    32 voxels; bias, out_stats; against fp64 on the bf16-rounded operands, and the moments against a gn_stats3d pass."""
+    32 voxels; bias, out_stats; against fp64 on the bf16-rounded operands, and the moments against a gn_stats3d pass.
+    Cin 256 -> Cout 128 is the one shape whose resident weights need more than 64 KiB of LDS."""
     from nps_hip import ops
     torch.manual_seed(13)
-    B, dhw = 2, (5, 9, 37)
     xs = []
     for k, (c, o) in enumerate(zip(chans, offs)):
         shp = tuple(n - 2 * oo for n, oo in zip(dhw, o))  # crop (< 0): larger; zero-pad (> 0): smaller

@@ -23,7 +23,7 @@ KERNELS = {
     "3x3": (196, 192, 3, 1, 1, 0, "zeros", 33, 35),               # conv2d_x3_kernel<9,*>
     "3x3_circ": (64, 64, 3, 1, 1, 1, "circular", 20, 24),         # circular frame extension
     "1x1_lds_weights": (196, 192, 1, 1, 1, 0, "zeros", 37, 29),   # conv1x1_wl_kernel
-    "1x1_coblock": (48, 388, 1, 1, 1, 0, "zeros", 15, 17),        # conv1x1_x3_kernel
+    "1x1_groups": (48, 388, 1, 1, 1, 0, "zeros", 15, 17),         # conv1x1_wl_kernel, 3 channel groups of 192
     "5x5_dilated": (132, 128, 5, 1, 4, "same", "circular", 40, 36),  # conv2d_x3_kernel<25,2> on the lattice
     "3x3_s2": (32, 32, 3, 2, 1, 0, "zeros", 31, 29),              # space-to-depth 2x2 (<4,*>)
 }

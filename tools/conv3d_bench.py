@@ -2,8 +2,8 @@
 
 python tools/conv3d_bench.py [--srcs 64,4 --cout 64 --k 1 --stride 1 --dhw 16,128,128 --b 8 --gn 0 --iters 20] [--save F]
 Prints HIP-event time, algorithmic TB/s (sources + weights + output, bf16) and TFLOP/s.  --save writes the output
-tensor (torch.save) so two processes with different dev knobs (e.g. NPS_C3D_1X1=0) can be compared bit for bit
-with --compare F.
+tensor (torch.save) so two processes with different libraries (NPS_HIP_LIB, tools/build_variant.sh) can be compared
+bit for bit with --compare F.
 """
 import argparse
 import os
@@ -65,12 +65,11 @@ def main():
     if a.pack_only:  # frame in, padded frame out
         nbytes = 2 * (sum(s.t.numel() for s in srcs) + y.numel())
     fl = 2.0 * nv * a.cout * cin * a.k ** 3
-    knob = os.environ.get("NPS_C3D_1X1", "1")
     if a.pack_only:
         print(f"frame_pack3d[bf16] srcs={a.srcs} dhw={a.dhw} B={a.b} gn={a.gn}: {ms * 1e3:.1f} us "
               f"{nbytes / ms / 1e9:.2f} TB/s", flush=True)
         fl = 0.0
-    print(f"conv3d[bf16] srcs={a.srcs} cout={a.cout} k={a.k} dhw={a.dhw} B={a.b} gn={a.gn} knob={knob}: {ms * 1e3:.1f} us "
+    print(f"conv3d[bf16] srcs={a.srcs} cout={a.cout} k={a.k} dhw={a.dhw} B={a.b} gn={a.gn}: {ms * 1e3:.1f} us "
           f"{nbytes / ms / 1e9:.2f} TB/s {fl / ms / 1e9:.1f} TFLOP/s", flush=True)
     if a.save:
         torch.save(y.cpu(), a.save)
