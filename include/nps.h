@@ -324,6 +324,56 @@ int nps_spectral_conv3d_bwd_nchw(const float* x, long x_bs, const float* w1, con
                                  float* dw2, float* dw3, float* dw4, void* ws, int B, int Cin, int Cout, int D, int H,
                                  int W, int m1, int m2, int m3, void* stream);
 
+/* ---- FiLM conditioning of SpectralConv2d (proc_fno.py:271-284, cond_mode "film") ----------------------
+ * The retained modes are multiplied by a real per-sample, per-channel, per-mode factor from the module's
+ * weights_feat = nn.Linear(K, N), N = Cout*2*m1*m2, applied to the conditioning vector p:
+ *  p [B][K] fp32, wf = weights_feat.weight [N][K], bias = weights_feat.bias [N],
+ *  F[b][n] = bias[n] + sum_k p[b][k] wf[n][k],  n(o, j, k2) = (o*2*m1 + j)*m2 + k2  (.view(B, Cout, 2*m1, m2)).
+ * Row j < m1 of F sits on frequency k1 = j (the [:m1] corner, "low"), row j >= m1 on k1 = H - 2*m1 + j (the
+ * [-m1:] corner, "high"); with 2*m1 > H a frequency can be both.
+ *  S [B][R][m2][Cout] real, the layout of Y:
+ *   transform_mode 0: S = 1 + [low] F(j_lo) + [high] F(j_hi)   (both terms where the corners overlap)
+ *   transform_mode 1: S = F(j_hi) if high, else F(j_lo)        (the second write wins, as for the weights)
+ * Errors (-1, text in nps_last_error): K outside [1, 64], transform_mode not 0 / 1, m1 > H, R > 32. */
+int nps_spectral_film_scale(const float* p, const float* wf, const float* bias, float* S, int B, int K, int Cout,
+                            int H, int m1, int m2, int transform_mode, void* stream);
+/* nps_spectral_mix with Y[b][r][k2][o] multiplied by S[b][r][k2][o] in the mixer's store (same kernels, same
+ * dispatch; S == 1 gives nps_spectral_mix's bits) */
+int nps_spectral_mix_scaled(const float* X2, const float* wpack, const float* S, float* Y, int B, int R, int m2,
+                            int Cin, int Cout, void* stream);
+/* Backward of Ys = Y * S.  Y [B][R][m2][Cout] complex: the UNSCALED mixer output (nps_spectral_mix of the saved X2;
+ * never Ys / S, S may be zero); g: the gradient arriving at Ys (PyTorch's convention), replaced in place by
+ * g * S = the gradient of Y; gS [B][R][m2][Cout] real (written) = Re Y Re g + Im Y Im g. */
+int nps_spectral_film_bwd(const float* Y, const float* S, float* g, float* gS, int B, int R, int m2, int Cout,
+                          void* stream);
+/* Gradients of the linear layer from gS, each output written or NULL = skipped: gwf [N][K] = sum_b gF[b][n] p[b][k],
+ * gbias [N] = sum_b gF[b][n], gp [B][K] = sum_n gF[b][n] wf[n][k], with gF[b][n(o, j, k2)] = gS[b][row(j)][k2][o]
+ * (zero, in transform_mode 1, for the rows j < m1 that the [-m1:] corner overwrote).  fp64 sums in a fixed order,
+ * no atomics: bit-repeatable. */
+int nps_spectral_film_param_bwd(const float* gS, const float* p, const float* wf, float* gwf, float* gbias, float* gp,
+                                int B, int K, int Cout, int H, int m1, int m2, int transform_mode, void* stream);
+/* The one-call composites with FiLM: nps_spectral_conv2d_fwd / _bwd and their channels-first forms with the
+ * operands p, wf, bias, K, transform_mode added (layouts, batch strides, accumulate / act, dx == NULL, dw1 / dw2
+ * both or neither as there); dp [B][K], dwf [N][K], dbias [N]: written, each NULL = skipped.  `ws` holds at least
+ * nps_spectral_conv2d_film_workspace() bytes (the plain workspace plus S, the unscaled Y and gS). */
+size_t nps_spectral_conv2d_film_workspace(int B, int Cin, int Cout, int H, int W, int m1, int m2);
+int nps_spectral_conv2d_film_fwd(const float* x, const float* w1, const float* w2, const float* p, const float* wf,
+                                 const float* bias, float* y, void* ws, int B, int Cin, int Cout, int H, int W,
+                                 int m1, int m2, int K, int transform_mode, int accumulate, int act, void* stream);
+int nps_spectral_conv2d_film_bwd(const float* x, const float* w1, const float* w2, const float* p, const float* wf,
+                                 const float* bias, const float* dy, float* dx, float* dw1, float* dw2, float* dp,
+                                 float* dwf, float* dbias, void* ws, int B, int Cin, int Cout, int H, int W, int m1,
+                                 int m2, int K, int transform_mode, void* stream);
+int nps_spectral_conv2d_film_fwd_nchw(const float* x, long x_bs, const float* w1, const float* w2, const float* p,
+                                      const float* wf, const float* bias, float* y, long y_bs, void* ws, int B,
+                                      int Cin, int Cout, int H, int W, int m1, int m2, int K, int transform_mode,
+                                      int accumulate, int act, void* stream);
+int nps_spectral_conv2d_film_bwd_nchw(const float* x, long x_bs, const float* w1, const float* w2, const float* p,
+                                      const float* wf, const float* bias, const float* dy, long dy_bs, float* dx,
+                                      long dx_bs, float* dw1, float* dw2, float* dp, float* dwf, float* dbias,
+                                      void* ws, int B, int Cin, int Cout, int H, int W, int m1, int m2, int K,
+                                      int transform_mode, void* stream);
+
 /* ---- bf16 storage (BASELINE config C5: the 3-D rFFT spectral conv in bf16) ----------------------------
  * Activations in HBM as bf16 (16-bit storage of NDHWC tensors viewed as (B, D*H, W, C)), every sum in fp32:
  * the same transforms as the fp32 entry points above.  Replaces the fp32 SpectralConv3d / FNO_Layer chain of

@@ -9,6 +9,7 @@
 // integer phase (k*n mod N)/N.
 #include "nps_common.hpp"
 
+#include <climits>
 #include <cstdlib>
 #include <type_traits>
 
@@ -345,9 +346,12 @@ __global__ void spec_pack_kernel(const float2* __restrict__ w1, const float2* __
         wp[i] = w1[(((size_t)ci * Cout + o) * m1 + k1) * m2 + k2];
 }
 
-// Y[b][mode][o] = sum_i X2[b][mode][i] * wp[mode][i][o]   (complex; mode = (r, k2))
+// Y[b][mode][o] = sum_i X2[b][mode][i] * wp[mode][i][o]   (complex; mode = (r, k2)).  SCALED: the FiLM factor
+// S[b][mode][o] (real, nps_spectral_film_scale) multiplies the sum in the store; the unscaled instantiation never
+// touches S.
+template <bool SCALED = false>
 __global__ void mix_kernel(const float2* __restrict__ X2, const float2* __restrict__ wp, float2* __restrict__ Y, int B,
-                           int nmodes, int Cin, int Cout) {
+                           int nmodes, int Cin, int Cout, const float* __restrict__ S) {
     extern __shared__ float2 xs[];  // [MAXB][Cin]
     const int mode = blockIdx.x;
     const int o = blockIdx.y * blockDim.x + threadIdx.x;
@@ -375,7 +379,15 @@ __global__ void mix_kernel(const float2* __restrict__ X2, const float2* __restri
             }
 #pragma unroll
             for (int bb = 0; bb < MAXB; ++bb)
-                if (bb < nb) Y[((size_t)(b0 + bb) * nmodes + mode) * Cout + o] = acc[bb];
+                if (bb < nb) {
+                    const size_t yi = ((size_t)(b0 + bb) * nmodes + mode) * Cout + o;
+                    if constexpr (SCALED) {
+                        const float sc = S[yi];
+                        Y[yi] = make_float2(acc[bb].x * sc, acc[bb].y * sc);
+                    } else {
+                        Y[yi] = acc[bb];
+                    }
+                }
         }
     }
 }
@@ -397,9 +409,12 @@ __device__ __forceinline__ float2 bf16x2_to_float2(unsigned v) {
     return make_float2(__uint_as_float(v << 16), __uint_as_float(v & 0xffff0000u));
 }
 
-template <typename WT, int NBC>
+// SCALED (fp32 path only): the FiLM factor S[b][mode][o] multiplies each output in the store epilogue; the
+// unscaled instantiations never touch S.
+template <typename WT, int NBC, bool SCALED = false>
 __global__ __launch_bounds__(256) void mix_mfma_kernel(const float2* __restrict__ X2, const WT* __restrict__ wp,
-                                                       float2* __restrict__ Y, int B, int nmodes, int Cin, int Cout) {
+                                                       float2* __restrict__ Y, int B, int nmodes, int Cin, int Cout,
+                                                       const float* __restrict__ S) {
     constexpr int WPT = MIX_IC * MIX_OC * (int)sizeof(WT) / (256 * 16);  // 16-B weight pieces per thread
     static_assert(WPT >= 1 && MIX_IC * MIX_OC * sizeof(WT) % (256 * 16) == 0, "weight chunk split");
     __shared__ float2 Ws[2][MIX_IC][MIX_OC];          // weight chunk, fp32 complex
@@ -486,8 +501,17 @@ __global__ __launch_bounds__(256) void mix_mfma_kernel(const float2* __restrict_
             for (int t = 0; t < 2; ++t) {
                 const int o = o0 + wave * 16 + t * 8 + 2 * (lane >> 4);
                 float2* y = Y + ((size_t)b * nmodes + mode) * Cout;
-                if (o < Cout) y[o] = make_float2(acc[n][t][0], acc[n][t][1]);
-                if (o + 1 < Cout) y[o + 1] = make_float2(acc[n][t][2], acc[n][t][3]);
+                if constexpr (SCALED) {
+                    // Cout % 4 == 0 and o even: o < Cout implies o + 1 < Cout, so the pair is one 8-B load
+                    if (o < Cout) {
+                        const float2 sc = *reinterpret_cast<const float2*>(S + ((size_t)b * nmodes + mode) * Cout + o);
+                        y[o] = make_float2(acc[n][t][0] * sc.x, acc[n][t][1] * sc.x);
+                        y[o + 1] = make_float2(acc[n][t][2] * sc.y, acc[n][t][3] * sc.y);
+                    }
+                } else {
+                    if (o < Cout) y[o] = make_float2(acc[n][t][0], acc[n][t][1]);
+                    if (o + 1 < Cout) y[o + 1] = make_float2(acc[n][t][2], acc[n][t][3]);
+                }
             }
         }
     }
@@ -821,6 +845,144 @@ __global__ void spec_unpack_grad_kernel(const float2* __restrict__ gwp, float2* 
     gw2[idx] = gwp[(((size_t)row_of(k1b) * m2 + k2) * Cin + ci) * Cout + o];
 }
 
+// ---- FiLM conditioning of the retained modes (proc_fno.py:271-284) ------------------------------------------
+// F[b][n] = bf[n] + sum_k p[b][k] Wf[n][k] with n(o, j, k2) = (o * 2 m1 + j) * m2 + k2 is the reference's
+// weights_feat(p).view(B, Cout, 2 m1, m2); row j < m1 sits on frequency k1 = j (the [:m1] corner), row j >= m1 on
+// k1 = H - 2 m1 + j (the [-m1:] corner).
+constexpr int FILM_OC = 64;    // output channels per work-group of the FiLM kernels
+constexpr int FILM_MAXK = 64;  // conditioning scalars (LDS: 2 corners x K x 64 channels of Wf)
+
+// the retained row of weights_feat row j, and whether transform_mode 1's second write ([-m1:]) replaced it
+__device__ __forceinline__ int film_row(int j, int H, int R, int m1) {
+    const int k1 = j < m1 ? j : H - 2 * m1 + j;
+    return k1 < m1 ? k1 : k1 - (H - R);
+}
+__device__ __forceinline__ bool film_dead(int j, int H, int m1, int mode) {
+    return mode == 1 && j < m1 && j >= H - m1;
+}
+
+// S[b][r][k2][o]: the real factor of Y.  transform_mode 0: 1 + [low] F(j_lo) + [high] F(j_hi) (the reference adds
+// the two corners one after the other, so an overlapping row gets both); 1: F(j_hi) if high, else F(j_lo).
+// Work-group = one (r, k2) x 64 output channels: the Wf rows of its one or two j (K contiguous floats per
+// channel, 2 m1 m2 K apart between channels) are staged once as [k][o] in LDS, then wave w forms batches w,
+// w + 4, ... with the K-sum in a register, p[b][k] wave-uniform, stores coalesced over o.
+__global__ __launch_bounds__(256) void film_scale_kernel(const float* __restrict__ p, const float* __restrict__ Wf,
+                                                         const float* __restrict__ bf, float* __restrict__ S, int B,
+                                                         int K, int Cout, int H, int R, int m1, int m2, int mode) {
+    extern __shared__ float film_lds[];  // Ws[2][K][FILM_OC], bs[2][FILM_OC]
+    float* Ws = film_lds;
+    float* bs = film_lds + 2 * K * FILM_OC;
+    const int r = blockIdx.x / m2, k2 = blockIdx.x - r * m2;
+    const int o0 = blockIdx.y * FILM_OC;
+    const int k1 = row_k1(r, H, R, m1);
+    const bool low = k1 < m1, high = k1 >= H - m1;
+    const int jsel[2] = {k1, k1 - (H - 2 * m1)};
+    const bool use[2] = {low, high};
+    for (int c = 0; c < 2; ++c) {
+        if (!use[c]) continue;
+        for (int e = threadIdx.x; e < FILM_OC * K; e += 256) {
+            const int ol = e / K, k = e - ol * K;
+            const int o = o0 + ol;
+            const size_t n = ((size_t)o * 2 * m1 + jsel[c]) * m2 + k2;
+            Ws[(c * K + k) * FILM_OC + ol] = o < Cout ? Wf[n * K + k] : 0.f;
+        }
+        if (threadIdx.x < FILM_OC) {
+            const int o = o0 + threadIdx.x;
+            bs[c * FILM_OC + threadIdx.x] = o < Cout ? bf[((size_t)o * 2 * m1 + jsel[c]) * m2 + k2] : 0.f;
+        }
+    }
+    __syncthreads();
+    const int ol = threadIdx.x & 63, o = o0 + ol;
+    if (o >= Cout) return;
+    for (int b = threadIdx.x >> 6; b < B; b += 4) {
+        const float* pb = p + (size_t)b * K;
+        float f[2] = {0.f, 0.f};
+#pragma unroll
+        for (int c = 0; c < 2; ++c) {
+            if (!use[c]) continue;
+            float acc = bs[c * FILM_OC + ol];
+            for (int k = 0; k < K; ++k) acc = fmaf(pb[k], Ws[(c * K + k) * FILM_OC + ol], acc);
+            f[c] = acc;
+        }
+        float s;
+        if (mode == 0)
+            s = 1.0f + f[0] + f[1];  // an unused corner contributes 0
+        else
+            s = high ? f[1] : f[0];
+        S[(((size_t)b * R + r) * m2 + k2) * Cout + o] = s;
+    }
+}
+
+// backward of Ys = Y * S at one element: gS = Re Y Re g + Im Y Im g on the unscaled Y, then g <- g * S in place
+__global__ void film_bwd_kernel(const float2* __restrict__ Y, const float* __restrict__ S, float2* __restrict__ g,
+                                float* __restrict__ gS, size_t n) {
+    const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n) return;
+    const float2 y = Y[i], gv = g[i];
+    const float s = S[i];
+    gS[i] = fmaf(y.x, gv.x, y.y * gv.y);
+    g[i] = make_float2(gv.x * s, gv.y * s);
+}
+
+// gWf[n][k] = sum_b gF[b][n] p[b][k], gbf[n] = sum_b gF[b][n] with gF[b][n(o, j, k2)] = gS[b][row(j)][k2][o]
+// (zero where transform_mode 1 overwrote row j): one thread per (n, k) walks the batch in order with an fp64 sum,
+// so the result is the same bits every run.  Work-group = one (j, k2) x 64 channels; lanes run over o (coalesced
+// gS reads), waves over k (k == K is the bias).
+__global__ __launch_bounds__(256) void film_wgrad_kernel(const float* __restrict__ gS, const float* __restrict__ p,
+                                                         float* __restrict__ gWf, float* __restrict__ gbf, int B, int K,
+                                                         int Cout, int H, int R, int m1, int m2, int mode) {
+    const int j = blockIdx.x / m2, k2 = blockIdx.x - j * m2;
+    const int o = blockIdx.y * FILM_OC + (threadIdx.x & 63);
+    if (o >= Cout) return;
+    const int r = film_row(j, H, R, m1);
+    const bool dead = film_dead(j, H, m1, mode);
+    const size_t n = ((size_t)o * 2 * m1 + j) * m2 + k2;
+    const float* gs = gS + ((size_t)r * m2 + k2) * Cout + o;
+    const size_t bstride = (size_t)R * m2 * Cout;
+    for (int k = threadIdx.x >> 6; k <= K; k += 4) {
+        float* dst = k < K ? (gWf ? gWf + n * K + k : nullptr) : (gbf ? gbf + n : nullptr);
+        if (dst == nullptr) continue;
+        double acc = 0.0;
+        if (!dead) {
+#pragma unroll 4
+            for (int b = 0; b < B; ++b)
+                acc += (double)gs[b * bstride] * (k < K ? (double)p[(size_t)b * K + k] : 1.0);
+        }
+        *dst = (float)acc;
+    }
+}
+
+// gp[b][k] = sum_n gF[b][n] Wf[n][k]: work-group (4 consecutive k, b) of 1024 threads; each thread sums the rows
+// n = tid, tid + 1024, ... in fp64 (lanes on neighbouring n, so the Wf reads coalesce and only the one gS value per
+// row is gathered: one cache line per lane), then one fixed-order block sum per k: two stages, no atomics, the same
+// bits every run.
+constexpr int FILM_PK = 4;
+__global__ __launch_bounds__(1024) void film_pgrad_kernel(const float* __restrict__ gS, const float* __restrict__ Wf,
+                                                          float* __restrict__ gp, int K, int Cout, int H, int R,
+                                                          int m1, int m2, int mode) {
+    __shared__ double scratch[16];
+    const int k0 = blockIdx.x * FILM_PK, b = blockIdx.y;
+    const int nk = min(FILM_PK, K - k0);
+    const int N = Cout * 2 * m1 * m2;  // (fits an int: host-checked)
+    double acc[FILM_PK] = {0.0, 0.0, 0.0, 0.0};
+    for (int n = threadIdx.x; n < N; n += 1024) {
+        const int k2 = n % m2, t = n / m2;
+        const int j = t % (2 * m1), o = t / (2 * m1);
+        if (film_dead(j, H, m1, mode)) continue;
+        const int r = film_row(j, H, R, m1);
+        const double gs = (double)gS[(((size_t)b * R + r) * m2 + k2) * Cout + o];
+        const float* w = Wf + (size_t)n * K + k0;
+#pragma unroll
+        for (int i = 0; i < FILM_PK; ++i)
+            if (i < nk) acc[i] += gs * (double)w[i];
+    }
+#pragma unroll
+    for (int i = 0; i < FILM_PK; ++i) {
+        const double tot = nps::block_sum(acc[i], scratch);  // (every thread takes part, also for i >= nk)
+        if (threadIdx.x == 0 && i < nk) gp[(size_t)b * K + k0 + i] = (float)tot;
+    }
+}
+
 
 size_t dft_w_lds(int m2, int W) { return sizeof(float2) * kc_for(m2) * W; }
 size_t idft_w_lds(int m2, int W) {
@@ -975,9 +1137,9 @@ extern "C" int nps_spectral_mix(const float* X2, const float* wpack, float* Y, i
         const auto* w = reinterpret_cast<const float2*>(wpack);
         auto* y = reinterpret_cast<float2*>(Y);
         if (B <= 16)
-            mix_mfma_kernel<float2, 1><<<grid, 256, 0, s>>>(x, w, y, B, nmodes, Cin, Cout);
+            mix_mfma_kernel<float2, 1><<<grid, 256, 0, s>>>(x, w, y, B, nmodes, Cin, Cout, nullptr);
         else
-            mix_mfma_kernel<float2, 2><<<grid, 256, 0, s>>>(x, w, y, B, nmodes, Cin, Cout);
+            mix_mfma_kernel<float2, 2><<<grid, 256, 0, s>>>(x, w, y, B, nmodes, Cin, Cout, nullptr);
         NPS_CHECK_LAUNCH("spectral_mix (MFMA)");
         return 0;
     }
@@ -985,9 +1147,110 @@ extern "C" int nps_spectral_mix(const float* X2, const float* wpack, float* Y, i
     NPS_CHECK_ARG(lds <= 64 * 1024, "spectral_mix: Cin=%d too large", Cin);
     const int bs = Cout >= 256 ? 256 : ((Cout + 63) / 64) * 64;
     dim3 grid(nmodes, (Cout + bs - 1) / bs);
-    mix_kernel<<<grid, bs, lds, s>>>(reinterpret_cast<const float2*>(X2), reinterpret_cast<const float2*>(wpack),
-                                     reinterpret_cast<float2*>(Y), B, nmodes, Cin, Cout);
+    mix_kernel<false><<<grid, bs, lds, s>>>(reinterpret_cast<const float2*>(X2),
+                                            reinterpret_cast<const float2*>(wpack), reinterpret_cast<float2*>(Y), B,
+                                            nmodes, Cin, Cout, nullptr);
     NPS_CHECK_LAUNCH("spectral_mix");
+    return 0;
+}
+
+// ---- FiLM (proc_fno.py:271-284): the scale stage, the scaled mixer and their backward -------------------------
+static bool film_args_ok(const char* what, int B, int K, int Cout, int H, int m1, int m2, int transform_mode) {
+    if (!(B > 0 && Cout > 0 && H > 0 && m2 > 0)) {
+        nps::set_error("%s: B, Cout, H and m2 must be positive (B=%d Cout=%d H=%d m2=%d)", what, B, Cout, H, m2);
+        return false;
+    }
+    if (!(K > 0 && K <= FILM_MAXK)) {
+        nps::set_error("%s: K (feature_transform_dim) must be in [1, %d], got %d", what, FILM_MAXK, K);
+        return false;
+    }
+    if (!(transform_mode == 0 || transform_mode == 1)) {
+        nps::set_error("%s: transform_mode is 0 (1 + FiLM) or 1 (FiLM), got %d", what, transform_mode);
+        return false;
+    }
+    if (!(m1 > 0 && m1 <= H)) {
+        nps::set_error("%s: modes should be at most the spatial dim (H=%d m1=%d)", what, H, m1);
+        return false;
+    }
+    if ((size_t)Cout * 2 * m1 * m2 > (size_t)INT_MAX) {
+        nps::set_error("%s: Cout*2*m1*m2 does not fit an int (Cout=%d m1=%d m2=%d)", what, Cout, m1, m2);
+        return false;
+    }
+    if ((H < 2 * m1 ? H : 2 * m1) > MAXR) {
+        nps::set_error("%s: %d retained rows > %d", what, H < 2 * m1 ? H : 2 * m1, MAXR);
+        return false;
+    }
+    return true;
+}
+
+extern "C" int nps_spectral_film_scale(const float* p, const float* wf, const float* bias, float* S, int B, int K,
+                                       int Cout, int H, int m1, int m2, int transform_mode, void* stream) {
+    NPS_CHECK_ARG(p && wf && bias && S, "spectral_film_scale: NULL pointer");
+    if (!film_args_ok("spectral_film_scale", B, K, Cout, H, m1, m2, transform_mode)) return -1;
+    const int R = H < 2 * m1 ? H : 2 * m1;
+    const size_t lds = sizeof(float) * 2 * FILM_OC * ((size_t)K + 1);
+    film_scale_kernel<<<dim3(R * m2, (Cout + FILM_OC - 1) / FILM_OC), 256, lds, (hipStream_t)stream>>>(
+        p, wf, bias, S, B, K, Cout, H, R, m1, m2, transform_mode);
+    NPS_CHECK_LAUNCH("spectral_film_scale");
+    return 0;
+}
+
+extern "C" int nps_spectral_mix_scaled(const float* X2, const float* wpack, const float* S, float* Y, int B, int R,
+                                       int m2, int Cin, int Cout, void* stream) {
+    NPS_CHECK_ARG(X2 && wpack && S && Y, "spectral_mix_scaled: NULL pointer");
+    NPS_CHECK_ARG(B > 0 && R > 0 && m2 > 0 && Cin > 0 && Cout > 0,
+                  "spectral_mix_scaled: sizes must be positive (B=%d R=%d m2=%d Cin=%d Cout=%d)", B, R, m2, Cin, Cout);
+    hipStream_t s = (hipStream_t)stream;
+    const int nmodes = R * m2;
+    const auto* x = reinterpret_cast<const float2*>(X2);
+    const auto* w = reinterpret_cast<const float2*>(wpack);
+    auto* y = reinterpret_cast<float2*>(Y);
+    if (!mix_valu() && (Cout & 3) == 0) {  // the dispatch of nps_spectral_mix
+        const dim3 grid(nmodes, (Cout + MIX_OC - 1) / MIX_OC);
+        if (B <= 16)
+            mix_mfma_kernel<float2, 1, true><<<grid, 256, 0, s>>>(x, w, y, B, nmodes, Cin, Cout, S);
+        else
+            mix_mfma_kernel<float2, 2, true><<<grid, 256, 0, s>>>(x, w, y, B, nmodes, Cin, Cout, S);
+        NPS_CHECK_LAUNCH("spectral_mix_scaled (MFMA)");
+        return 0;
+    }
+    const size_t lds = sizeof(float2) * MAXB * Cin;
+    NPS_CHECK_ARG(lds <= 64 * 1024, "spectral_mix_scaled: Cin=%d too large", Cin);
+    const int bs = Cout >= 256 ? 256 : ((Cout + 63) / 64) * 64;
+    mix_kernel<true><<<dim3(nmodes, (Cout + bs - 1) / bs), bs, lds, s>>>(x, w, y, B, nmodes, Cin, Cout, S);
+    NPS_CHECK_LAUNCH("spectral_mix_scaled");
+    return 0;
+}
+
+extern "C" int nps_spectral_film_bwd(const float* Y, const float* S, float* g, float* gS, int B, int R, int m2,
+                                     int Cout, void* stream) {
+    NPS_CHECK_ARG(Y && S && g && gS, "spectral_film_bwd: NULL pointer");
+    NPS_CHECK_ARG(B > 0 && R > 0 && m2 > 0 && Cout > 0,
+                  "spectral_film_bwd: sizes must be positive (B=%d R=%d m2=%d Cout=%d)", B, R, m2, Cout);
+    const size_t n = (size_t)B * R * m2 * Cout;
+    film_bwd_kernel<<<(unsigned)((n + 255) / 256), 256, 0, (hipStream_t)stream>>>(
+        reinterpret_cast<const float2*>(Y), S, reinterpret_cast<float2*>(g), gS, n);
+    NPS_CHECK_LAUNCH("spectral_film_bwd");
+    return 0;
+}
+
+extern "C" int nps_spectral_film_param_bwd(const float* gS, const float* p, const float* wf, float* gwf, float* gbias,
+                                           float* gp, int B, int K, int Cout, int H, int m1, int m2,
+                                           int transform_mode, void* stream) {
+    NPS_CHECK_ARG(gS && p && wf, "spectral_film_param_bwd: NULL pointer");
+    if (!film_args_ok("spectral_film_param_bwd", B, K, Cout, H, m1, m2, transform_mode)) return -1;
+    const int R = H < 2 * m1 ? H : 2 * m1;
+    hipStream_t s = (hipStream_t)stream;
+    if (gwf != nullptr || gbias != nullptr) {
+        film_wgrad_kernel<<<dim3(2 * m1 * m2, (Cout + FILM_OC - 1) / FILM_OC), 256, 0, s>>>(
+            gS, p, gwf, gbias, B, K, Cout, H, R, m1, m2, transform_mode);
+        NPS_CHECK_LAUNCH("spectral_film_param_bwd (weights_feat)");
+    }
+    if (gp != nullptr) {
+        film_pgrad_kernel<<<dim3((K + FILM_PK - 1) / FILM_PK, B), 1024, 0, s>>>(gS, wf, gp, K, Cout, H, R, m1, m2,
+                                                                                transform_mode);
+        NPS_CHECK_LAUNCH("spectral_film_param_bwd (p)");
+    }
     return 0;
 }
 
@@ -1091,9 +1354,9 @@ extern "C" int nps_spectral_mix_bf16(const float* X2, const void* wpack, float* 
     const auto* w = reinterpret_cast<const unsigned*>(wpack);
     auto* y = reinterpret_cast<float2*>(Y);
     if (B <= 16)
-        mix_mfma_kernel<unsigned, 1><<<grid, 256, 0, (hipStream_t)stream>>>(x, w, y, B, nmodes, Cin, Cout);
+        mix_mfma_kernel<unsigned, 1><<<grid, 256, 0, (hipStream_t)stream>>>(x, w, y, B, nmodes, Cin, Cout, nullptr);
     else
-        mix_mfma_kernel<unsigned, 2><<<grid, 256, 0, (hipStream_t)stream>>>(x, w, y, B, nmodes, Cin, Cout);
+        mix_mfma_kernel<unsigned, 2><<<grid, 256, 0, (hipStream_t)stream>>>(x, w, y, B, nmodes, Cin, Cout, nullptr);
     NPS_CHECK_LAUNCH("spectral_mix_bf16");
     return 0;
 }

@@ -43,6 +43,33 @@ size_t spec2_ws(int B, int Cin, int Cout, int H, int m1, int m2) {
     return al256(s.wp) + al256(s.x1) + al256(s.x2) + al256(s.y) + al256(s.z) + al256(s.x2) + al256(s.wp);
 }
 
+// FiLM operands of a composite (proc_fno.py:271-284): p [B][K], weights_feat.weight [Cout*2*m1*m2][K], its bias, and
+// transform_mode.  The FiLM composites append [S][Yu][gS] to the plain workspace: the factor S [B][R][m2][Cout]
+// (real), and for the backward the unscaled mixer output Yu (complex) and gS (real).
+struct Film {
+    const float *p, *wf, *bias;
+    int K, mode;
+};
+// the host checks of nps_spectral_film_scale / _param_bwd (spectral.hip), made before a composite's first launch
+bool film_ok(const char* what, const Film& f, int H, int m1) {
+    const int R = H < 2 * m1 ? H : 2 * m1;
+    if (!(f.p && f.wf && f.bias))
+        nps::set_error("%s: NULL FiLM pointer (p, wf, bias)", what);
+    else if (!(f.K > 0 && f.K <= 64))
+        nps::set_error("%s: K (feature_transform_dim) must be in [1, 64], got %d", what, f.K);
+    else if (!(f.mode == 0 || f.mode == 1))
+        nps::set_error("%s: transform_mode is 0 (1 + FiLM) or 1 (FiLM), got %d", what, f.mode);
+    else if (R > 32)
+        nps::set_error("%s: %d retained rows > 32", what, R);
+    else
+        return true;
+    return false;
+}
+size_t film_ws(int B, int Cin, int Cout, int H, int m1, int m2) {
+    const Spec2 s = spec2_sizes(B, Cin, Cout, H, m1, m2);
+    return spec2_ws(B, Cin, Cout, H, m1, m2) + al256(s.y / 2) + al256(s.y) + al256(s.y / 2);
+}
+
 bool spec2_args_ok(int B, int Cin, int Cout, int H, int W, int m1, int m2) {
     // proc_fno.py:134-139: modes at most the spatial dims (W // 2 + 1 for the last)
     return B > 0 && Cin > 0 && Cout > 0 && H > 0 && W > 0 && m1 > 0 && m2 > 0 && m1 <= H && m2 <= W / 2 + 1;
@@ -78,7 +105,8 @@ int w_dft_bwd(const float* gX1, float* dx, Lay l, int B, int R, int W, int m, in
 // Z = the spectral conv up to its W-pass synthesis, for the frame `src` (nsrc sources covering B x H x W x Cin; one
 // channels-first tensor when xl.nchw)
 int spec2_z(const nps_src_t* src, int nsrc, Lay xl, const float* w1, const float* w2, Carve& c, const Spec2& sz, int B,
-            int Cin, int Cout, int H, int W, int m1, int m2, float** Zout, float** X2out, float** wpout, void* s) {
+            int Cin, int Cout, int H, int W, int m1, int m2, float** Zout, float** X2out, float** wpout, void* s,
+            const Film* film = nullptr, float* S = nullptr) {
     const int R = H < 2 * m1 ? H : 2 * m1;
     float* wp = c.take(sz.wp);
     float* X1 = c.take(sz.x1);
@@ -89,7 +117,14 @@ int spec2_z(const nps_src_t* src, int nsrc, Lay xl, const float* w1, const float
     if ((rc = nps_spectral_pack_weights(w1, w2, wp, Cin, Cout, H, m1, m2, s)) < 0) return rc;
     if ((rc = w_dft(src, nsrc, xl, B, H, W, Cin, m2, X1, s)) < 0) return rc;
     if ((rc = nps_spectral_dft_h(X1, X2, B, H, m1, m2, Cin, s)) < 0) return rc;
-    if ((rc = nps_spectral_mix(X2, wp, Y, B, R, m2, Cin, Cout, s)) < 0) return rc;
+    if (film != nullptr) {  // Y <- Y * S in the mixer's store
+        if ((rc = nps_spectral_film_scale(film->p, film->wf, film->bias, S, B, film->K, Cout, H, m1, m2, film->mode,
+                                          s)) < 0)
+            return rc;
+        if ((rc = nps_spectral_mix_scaled(X2, wp, S, Y, B, R, m2, Cin, Cout, s)) < 0) return rc;
+    } else if ((rc = nps_spectral_mix(X2, wp, Y, B, R, m2, Cin, Cout, s)) < 0) {
+        return rc;
+    }
     if ((rc = nps_spectral_idft_h(Y, Z, B, H, m1, m2, Cout, s)) < 0) return rc;
     *Zout = Z;
     if (X2out) *X2out = X2;
@@ -144,8 +179,10 @@ namespace {
 
 // The 2-D composites for either layout (`what` names the entry point in the error text)
 int conv2d_fwd(const char* what, const float* x, Lay xl, const float* w1, const float* w2, float* y, Lay yl, void* ws,
-               int B, int Cin, int Cout, int H, int W, int m1, int m2, int accumulate, int act, void* stream) {
+               int B, int Cin, int Cout, int H, int W, int m1, int m2, int accumulate, int act, void* stream,
+               const Film* film = nullptr) {
     NPS_CHECK_ARG(x && w1 && w2 && y && ws, "%s: NULL pointer", what);
+    if (film != nullptr && !film_ok(what, *film, H, m1)) return -1;  // before the first launch
     NPS_CHECK_ARG(spec2_args_ok(B, Cin, Cout, H, W, m1, m2),
                   "%s: modes should be at most the spatial dim (// 2 + 1 for the last spatial "
                   "dimension) (H=%d W=%d m1=%d m2=%d)", what, H, W, m1, m2);
@@ -157,15 +194,19 @@ int conv2d_fwd(const char* what, const float* x, Lay xl, const float* w1, const 
     Carve c{static_cast<char*>(ws)};
     const Spec2 sz = spec2_sizes(B, Cin, Cout, H, m1, m2);
     float* Z = nullptr;
-    int rc = spec2_z(&src, 1, xl, w1, w2, c, sz, B, Cin, Cout, H, W, m1, m2, &Z, nullptr, nullptr, stream);
+    // the FiLM factor lies behind the plain workspace (film_ws)
+    float* S = film ? reinterpret_cast<float*>(static_cast<char*>(ws) + spec2_ws(B, Cin, Cout, H, m1, m2)) : nullptr;
+    int rc = spec2_z(&src, 1, xl, w1, w2, c, sz, B, Cin, Cout, H, W, m1, m2, &Z, nullptr, nullptr, stream, film, S);
     if (rc < 0) return rc;
     return w_idft(Z, y, yl, B, H, W, m2, Cout, accumulate ? 1 : 0, act, stream);
 }
 
 int conv2d_bwd(const char* what, const float* x, Lay xl, const float* w1, const float* w2, const float* dy, Lay dyl,
                float* dx, Lay dxl, float* dw1, float* dw2, void* ws, int B, int Cin, int Cout, int H, int W, int m1,
-               int m2, void* stream) {
+               int m2, void* stream, const Film* film = nullptr, float* dp = nullptr, float* dwf = nullptr,
+               float* dbias = nullptr) {
     NPS_CHECK_ARG(x && w1 && w2 && dy && ws, "%s: NULL pointer", what);
+    if (film != nullptr && !film_ok(what, *film, H, m1)) return -1;  // before the first launch
     NPS_CHECK_ARG((dw1 == nullptr) == (dw2 == nullptr), "%s: dw1 and dw2 are both given or both NULL", what);
     NPS_CHECK_ARG(spec2_args_ok(B, Cin, Cout, H, W, m1, m2), "%s: bad shape (H=%d W=%d m1=%d m2=%d)", what, H, W, m1,
                   m2);
@@ -184,6 +225,9 @@ int conv2d_bwd(const char* what, const float* x, Lay xl, const float* w1, const 
     float* gZ = c.take(sz.z);
     float* gX2 = c.take(sz.x2);
     float* gwp = c.take(sz.wp);
+    float* S = film ? c.take(sz.y / 2) : nullptr;  // FiLM only (film_ws)
+    float* Yu = film ? c.take(sz.y) : nullptr;
+    float* gS = film ? c.take(sz.y / 2) : nullptr;
     const nps_src_t src = {x, Cin, H, W, 0, 0};
     int rc;
     // the forward's retained spectrum X2 (mix_bwd's conj(X2) for the weight gradient) and the packed weight
@@ -193,6 +237,18 @@ int conv2d_bwd(const char* what, const float* x, Lay xl, const float* w1, const 
     // adjoint chain: irfft2's adjoint, the H pass, the mixing's two adjoint products
     if ((rc = w_idft_bwd(dy, dyl, gZ, B, H, W, m2, Cout, stream)) < 0) return rc;
     if ((rc = nps_spectral_dft_h(gZ, gY, B, H, m1, m2, Cout, stream)) < 0) return rc;
+    if (film != nullptr) {
+        // the factor and the unscaled mixer output again (never Y / S: S may be zero); gS from them, gY <- gY * S
+        if ((rc = nps_spectral_film_scale(film->p, film->wf, film->bias, S, B, film->K, Cout, H, m1, m2, film->mode,
+                                          stream)) < 0)
+            return rc;
+        if ((rc = nps_spectral_mix(X2, wp, Yu, B, R, m2, Cin, Cout, stream)) < 0) return rc;
+        if ((rc = nps_spectral_film_bwd(Yu, S, gY, gS, B, R, m2, Cout, stream)) < 0) return rc;
+        if (dp != nullptr || dwf != nullptr || dbias != nullptr)
+            if ((rc = nps_spectral_film_param_bwd(gS, film->p, film->wf, dwf, dbias, dp, B, film->K, Cout, H, m1, m2,
+                                                  film->mode, stream)) < 0)
+                return rc;
+    }
     if ((rc = nps_spectral_mix_bwd(X2, wp, gY, gX2, gwp, B, R, m2, Cin, Cout, stream)) < 0) return rc;
     if (dx != nullptr) {
         if ((rc = nps_spectral_idft_h(gX2, X1, B, H, m1, m2, Cin, stream)) < 0) return rc;
@@ -232,6 +288,50 @@ extern "C" int nps_spectral_conv2d_bwd_nchw(const float* x, long x_bs, const flo
                                             int m2, void* stream) {
     return conv2d_bwd("spectral_conv2d_bwd_nchw", x, Lay{true, x_bs}, w1, w2, dy, Lay{true, dy_bs}, dx,
                       Lay{true, dx_bs}, dw1, dw2, ws, B, Cin, Cout, H, W, m1, m2, stream);
+}
+
+extern "C" size_t nps_spectral_conv2d_film_workspace(int B, int Cin, int Cout, int H, int W, int m1, int m2) {
+    if (!spec2_args_ok(B, Cin, Cout, H, W, m1, m2)) return 0;
+    return film_ws(B, Cin, Cout, H, m1, m2);
+}
+
+extern "C" int nps_spectral_conv2d_film_fwd(const float* x, const float* w1, const float* w2, const float* p,
+                                            const float* wf, const float* bias, float* y, void* ws, int B, int Cin,
+                                            int Cout, int H, int W, int m1, int m2, int K, int transform_mode,
+                                            int accumulate, int act, void* stream) {
+    const Film f = {p, wf, bias, K, transform_mode};
+    return conv2d_fwd("spectral_conv2d_film_fwd", x, NHWC, w1, w2, y, NHWC, ws, B, Cin, Cout, H, W, m1, m2, accumulate,
+                      act, stream, &f);
+}
+
+extern "C" int nps_spectral_conv2d_film_fwd_nchw(const float* x, long x_bs, const float* w1, const float* w2,
+                                                 const float* p, const float* wf, const float* bias, float* y,
+                                                 long y_bs, void* ws, int B, int Cin, int Cout, int H, int W, int m1,
+                                                 int m2, int K, int transform_mode, int accumulate, int act,
+                                                 void* stream) {
+    const Film f = {p, wf, bias, K, transform_mode};
+    return conv2d_fwd("spectral_conv2d_film_fwd_nchw", x, Lay{true, x_bs}, w1, w2, y, Lay{true, y_bs}, ws, B, Cin,
+                      Cout, H, W, m1, m2, accumulate, act, stream, &f);
+}
+
+extern "C" int nps_spectral_conv2d_film_bwd(const float* x, const float* w1, const float* w2, const float* p,
+                                            const float* wf, const float* bias, const float* dy, float* dx, float* dw1,
+                                            float* dw2, float* dp, float* dwf, float* dbias, void* ws, int B, int Cin,
+                                            int Cout, int H, int W, int m1, int m2, int K, int transform_mode,
+                                            void* stream) {
+    const Film f = {p, wf, bias, K, transform_mode};
+    return conv2d_bwd("spectral_conv2d_film_bwd", x, NHWC, w1, w2, dy, NHWC, dx, NHWC, dw1, dw2, ws, B, Cin, Cout, H, W,
+                      m1, m2, stream, &f, dp, dwf, dbias);
+}
+
+extern "C" int nps_spectral_conv2d_film_bwd_nchw(const float* x, long x_bs, const float* w1, const float* w2,
+                                                 const float* p, const float* wf, const float* bias, const float* dy,
+                                                 long dy_bs, float* dx, long dx_bs, float* dw1, float* dw2, float* dp,
+                                                 float* dwf, float* dbias, void* ws, int B, int Cin, int Cout, int H,
+                                                 int W, int m1, int m2, int K, int transform_mode, void* stream) {
+    const Film f = {p, wf, bias, K, transform_mode};
+    return conv2d_bwd("spectral_conv2d_film_bwd_nchw", x, Lay{true, x_bs}, w1, w2, dy, Lay{true, dy_bs}, dx,
+                      Lay{true, dx_bs}, dw1, dw2, ws, B, Cin, Cout, H, W, m1, m2, stream, &f, dp, dwf, dbias);
 }
 
 extern "C" size_t nps_fno_layer2d_workspace(int B, int Cin, int Cout, int H, int W, int m1, int m2) {

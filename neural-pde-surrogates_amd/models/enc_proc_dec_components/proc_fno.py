@@ -44,22 +44,35 @@ class FNO(nn.Module):
     def __repr__(self):
         return f'FNO{self.num_spatial_dims}D'
 
-    def run(self, h, vb, D=None):
-        """NHWC: h (B,H,W,C), vb (B,H,W,K) or None (3-D: NDHWC viewed as (B, D*H, W, C), depth D)."""
-        if self.cond_mode == "film":
-            raise NotImplementedError("FiLM conditioning is not on the MI355X path (twophase cfgs use concat)")
+    def _film_p(self, variables):
+        """The layers' FiLM operand: `variables` (B, n_cond) for cond_mode "film" with n_cond > 0, else None."""
+        if self.cond_mode != "film" or not self.fno_layers[0].conv.feature_transform:
+            return None  # film with n_cond == 0 is a plain FNO
+        if self.num_spatial_dims != 2:
+            raise NotImplementedError(SpectralConv3d.FILM_MSG if self.num_spatial_dims == 3 else
+                                      "FiLM conditioning is on the MI355X path for 2-D FNOs only")
+        if variables is None:
+            raise NotImplementedError(
+                "FNO(cond_mode='film') needs `variables` (B, n_cond): call forward(h, variables=...).  The reference "
+                "does not route `variables` to processors either (EncProcDec hands them variables_broadcast only), "
+                "so FiLM is a module-level feature")
+        return variables
+
+    def run(self, h, vb, D=None, variables=None):
+        """NHWC: h (B,H,W,C), vb (B,H,W,K) or None (3-D: NDHWC viewed as (B, D*H, W, C), depth D); variables (B,
+        n_cond): the FiLM operand of cond_mode "film"."""
+        p = self._film_p(variables)
         for layer in self.fno_layers:
             srcs = [ops.Src(h)] + ([ops.Src(vb)] if (vb is not None and self.cond_mode == "concat") else [])
-            h = layer.run(srcs, D=D) if self.num_spatial_dims == 3 else layer.run(srcs)
+            h = layer.run(srcs, D=D) if self.num_spatial_dims == 3 else layer.run(srcs, p=p)
         return h
 
-    def run_ad(self, h, vb, D=None):
-        if self.cond_mode == "film":
-            raise NotImplementedError("FiLM conditioning is not on the MI355X path (twophase cfgs use concat)")
+    def run_ad(self, h, vb, D=None, variables=None):
+        p = self._film_p(variables)
         for layer in self.fno_layers:
             srcs = [ops.Src(h)] + ([ops.Src(vb)] if (vb is not None and self.cond_mode == "concat") else [])
             x = ad.frame(srcs, h.shape[1:3])
-            h = layer.run_ad(x, D) if self.num_spatial_dims == 3 else layer.run_ad(x)
+            h = layer.run_ad(x, D) if self.num_spatial_dims == 3 else layer.run_ad(x, p=p)
         return h
 
     def run_bf16(self, h, vb, D):
@@ -68,7 +81,7 @@ class FNO(nn.Module):
         if self.num_spatial_dims != 3:
             raise NotImplementedError("the bf16 storage path is the 3-D FNO's (config C5)")
         if self.cond_mode == "film":
-            raise NotImplementedError("FiLM conditioning is not on the MI355X path (twophase cfgs use concat)")
+            raise NotImplementedError("FiLM conditioning is not on the bf16 storage path")
         for layer in self.fno_layers:
             srcs = [ops.Src(h)] + ([ops.Src(vb)] if (vb is not None and self.cond_mode == "concat") else [])
             h = layer.run_bf16(srcs, D)
@@ -76,6 +89,7 @@ class FNO(nn.Module):
 
     def forward(self, h: torch.Tensor, variables: torch.Tensor = None, variables_broadcast: torch.Tensor = None,
                 pos=None):
+        self._film_p(variables)  # a FiLM FNO without `variables`, or in 3-D, raises before any work
         if self.num_spatial_dims == 3:  # (B, C, D, H, W): the layers run on the (B, D*H, W, C) view
             B, C, D, H, W = h.shape
             flat = lambda t: t.reshape(t.shape[0], t.shape[1], D * H, W)
@@ -97,9 +111,9 @@ class FNO(nn.Module):
             return y.reshape(B, y.shape[1], D, H, W)
         if use_autograd(self):
             vb = ad.to_nhwc(variables_broadcast) if variables_broadcast is not None else None
-            return ad.to_nchw(self.run_ad(ad.to_nhwc(h), vb))
+            return ad.to_nchw(self.run_ad(ad.to_nhwc(h), vb, variables=variables))
         vb = ops.nchw_to_nhwc(variables_broadcast) if variables_broadcast is not None else None
-        return ops.nhwc_to_nchw(self.run(ops.nchw_to_nhwc(h), vb))
+        return ops.nhwc_to_nchw(self.run(ops.nchw_to_nhwc(h), vb, variables=variables))
 
 
 class FNO_Layer(nn.Module):
@@ -145,9 +159,9 @@ class FNO_Layer(nn.Module):
             else:
                 assert self.modes[i] <= s, 'modes should be at most the spatial dim all but the last spatial dimensions!'
 
-    def run(self, srcs, act_override=None, D=None):
-        """srcs: virtual NHWC input frame (h, vb) — for 3-D layers NDHWC sources viewed as (B, D*H, W, C).
-        Returns act(spectral(x) + w(x) [+ w2(x)])."""
+    def run(self, srcs, act_override=None, D=None, p=None):
+        """srcs: virtual NHWC input frame (h, vb) — for 3-D layers NDHWC sources viewed as (B, D*H, W, C); p (B, K):
+        the FiLM operand of a 2-D layer with feature_transform.  Returns act(spectral(x) + w(x) [+ w2(x)])."""
         if self.num_spatial_dims == 3:
             DH, W = srcs[0].t.shape[1:3]
             self._check_modes((D, DH // D, W))
@@ -161,16 +175,16 @@ class FNO_Layer(nn.Module):
         H, W = srcs[0].t.shape[1:3]
         self._check_modes((H, W))
         act = activation_code(self.act) if act_override is None else act_override
-        if (self.conv_mode != "double" and not self.conv.feature_transform and
-                ops.spectral_fusable(W, self.conv.modes2, self.conv.out_channels)):
+        if self.conv_mode != "double" and ops.spectral_fusable(W, self.conv.modes2, self.conv.out_channels):
             # conv(x) + w(x) in one output pass: the 1x1's epilogue synthesises the spectral conv's W pass
-            # (nps_conv2d_t.spec_z; scale 1 / (H W) of irfft2's norm), then the activation
-            Z = self.conv.run_z(srcs)
+            # (nps_conv2d_t.spec_z; scale 1 / (H W) of irfft2's norm), then the activation.  FiLM acts on the mixed
+            # modes, before Z is formed, so a FiLM layer takes the same route
+            Z = self.conv.run_z(srcs, p=p)
             return self.w.run(srcs, (H, W), spec=(Z, self.conv.modes2, 1.0 / (H * W)), act=act)
         out = self.w.run(srcs, (H, W))
         if self.conv_mode == "double":
             self.w2.run(srcs, (H, W), out=out, accumulate=True)
-        return self.conv.run(srcs, out=out, accumulate=True, act=act)
+        return self.conv.run(srcs, out=out, accumulate=True, act=act, p=p)
 
     def run_bf16(self, srcs, D, act_override=None):
         """3-D layer in bf16 storage: act(spectral(x) + w(x)) with bf16 sources / output, fp32 sums."""
@@ -182,8 +196,8 @@ class FNO_Layer(nn.Module):
         out = self.w.run_bf16(srcs)
         return self.conv.run_bf16(srcs, D, out=out, accumulate=True, act=act)
 
-    def run_ad(self, x, D=None):
-        """Differentiable form: x (B,H,W,Cin) materialised frame ((B, D*H, W, Cin) for 3-D layers)."""
+    def run_ad(self, x, D=None, p=None):
+        """Differentiable form: x (B,H,W,Cin) materialised frame ((B, D*H, W, Cin) for 3-D layers); p as in run."""
         if self.num_spatial_dims == 3:
             DH, W = x.shape[1:3]
             self._check_modes((D, DH // D, W))
@@ -194,13 +208,17 @@ class FNO_Layer(nn.Module):
         if self.num_spatial_dims != 2:
             raise NotImplementedError("FNO_Layer: 2-D / 3-D only on the MI355X path")
         self._check_modes(x.shape[1:3])
-        y = ad.add_at(ad.spectral_conv2d(self.conv, x), ad.conv2d(self.w, x))
+        spec = (ad.spectral_conv2d_film(self.conv, x, p) if self.conv.feature_transform
+                else ad.spectral_conv2d(self.conv, x))
+        y = ad.add_at(spec, ad.conv2d(self.w, x))
         if self.conv_mode == "double":
             y = ad.add_at(y, ad.conv2d(self.w2, x))
         return ad.act(y, activation_code(self.act))
 
     def forward(self, x, p=None):
         if self.num_spatial_dims == 3:
+            if self.conv.feature_transform:
+                raise NotImplementedError(SpectralConv3d.FILM_MSG)
             B, C, D, H, W = x.shape
             x4 = x.reshape(B, C, D * H, W)
             if use_autograd(self):
@@ -209,9 +227,9 @@ class FNO_Layer(nn.Module):
                 y = ops.nhwc_to_nchw(self.run([ops.Src(ops.nchw_to_nhwc(x4))], D=D))
             return y.reshape(B, y.shape[1], D, H, W)
         if use_autograd(self):
-            return ad.to_nchw(self.run_ad(ad.to_nhwc(x)))
+            return ad.to_nchw(self.run_ad(ad.to_nhwc(x), p=p))
         x = ops.nchw_to_nhwc(x)
-        return ops.nhwc_to_nchw(self.run([ops.Src(x)]))
+        return ops.nhwc_to_nchw(self.run([ops.Src(x)], p=p))
 
 
 class SpectralConv2d(nn.Module):
@@ -243,31 +261,34 @@ class SpectralConv2d(nn.Module):
             self._pk_key = key
         return self._pk
 
-    def run(self, srcs, out=None, accumulate=False, addend=None, act=0):
-        if self.feature_transform:
-            raise NotImplementedError("FiLM spectral conditioning is not on the MI355X path")
+    def film(self, p):
+        """ops' FiLM operand (p, weights_feat.weight, weights_feat.bias, transform_mode); None without
+        feature_transform (p is then ignored, as in the reference)."""
+        if not self.feature_transform:
+            return None
+        assert p is not None  # proc_fno.py:272: we must have supplied params
+        return (p, self.weights_feat.weight, self.weights_feat.bias, self.transform_mode)
+
+    def run(self, srcs, out=None, accumulate=False, addend=None, act=0, p=None):
         H = srcs[0].t.shape[1]
         return ops.spectral_conv2d(srcs, self.packed(H), self.modes1, self.modes2, self.out_channels, out=out,
-                                   accumulate=accumulate, addend=addend, act=act)
+                                   accumulate=accumulate, addend=addend, act=act, film=self.film(p))
 
-    def run_z(self, srcs):
+    def run_z(self, srcs, p=None):
         """The spectrum Z (B, H, m2, Cout) before the W-pass synthesis (ops.spectral_z): the FNO layer hands it to
         its 1x1 `w`, whose epilogue synthesises it (conv2d(spec=...))."""
-        if self.feature_transform:
-            raise NotImplementedError("FiLM spectral conditioning is not on the MI355X path")
         H = srcs[0].t.shape[1]
-        return ops.spectral_z(srcs, self.packed(H), self.modes1, self.modes2, self.out_channels)
+        return ops.spectral_z(srcs, self.packed(H), self.modes1, self.modes2, self.out_channels, film=self.film(p))
 
     def forward(self, x, p=None):
-        if self.feature_transform:
-            raise NotImplementedError("FiLM spectral conditioning is not on the MI355X path")
+        film = self.film(p)
         # the module's own NCHW tensors go straight to the channels-first W passes: no layout round trip
         H, W = x.shape[2:4]
         if not (self.modes1 <= H and self.modes2 <= W // 2 + 1):
             raise AssertionError("modes should be at most the spatial dim (// 2 + 1 for the last spatial dimension)")
         if use_autograd(self):
-            return ad.spectral_conv2d_nchw(self, x)
-        return ops.spectral_conv2d_nchw(x, self.packed(H), self.modes1, self.modes2, self.out_channels)
+            return ad.spectral_conv2d_nchw(self, x) if film is None else ad.spectral_conv2d_film_nchw(self, x, p)
+        return ops.spectral_conv2d_nchw(x, self.packed(H), self.modes1, self.modes2, self.out_channels, film=film)
 
 
 class SpectralConv1d(nn.Module):
@@ -293,6 +314,8 @@ class SpectralConv1d(nn.Module):
 class SpectralConv3d(nn.Module):
     """proc_fno.py:291-376: rfftn over (D, H, W) -> per-mode complex mixing of the 4 retained corners ->
     irfftn, on the per-axis truncated-DFT HIP pipeline (include/nps.h, SpectralConv3d)."""
+    FILM_MSG = ("SpectralConv3d FiLM is not built: the reference's own branch (proc_fno.py:351-370) cannot run (its "
+                "shapes mismatch unless modes3 == W // 2 + 1, and it writes the same slice four times)")
 
     def __init__(self, in_channels, out_channels, modes: tuple, feature_transform=False, feature_transform_dim=6,
                  transform_mode=1):
@@ -331,7 +354,7 @@ class SpectralConv3d(nn.Module):
     def run_bf16(self, srcs, D, out=None, accumulate=False, addend=None, act=0):
         """bf16-storage form: bf16 NDHWC sources viewed as (B, D*H, W, C) -> bf16 (B, D*H, W, Cout)."""
         if self.feature_transform:
-            raise NotImplementedError("FiLM spectral conditioning is not on the MI355X path")
+            raise NotImplementedError(self.FILM_MSG)
         H = srcs[0].t.shape[1] // D
         return ops.spectral_conv3d_bf16(srcs, D, self.packed_bf16(D, H), self.modes1, self.modes2, self.modes3,
                                         self.out_channels, out=out, accumulate=accumulate, addend=addend, act=act)
@@ -339,14 +362,14 @@ class SpectralConv3d(nn.Module):
     def run(self, srcs, D, out=None, accumulate=False, addend=None, act=0):
         """srcs: NDHWC sources viewed as (B, D*H, W, C).  Returns (B, D*H, W, Cout)."""
         if self.feature_transform:
-            raise NotImplementedError("FiLM spectral conditioning is not on the MI355X path")
+            raise NotImplementedError(self.FILM_MSG)
         H = srcs[0].t.shape[1] // D
         return ops.spectral_conv3d(srcs, D, self.packed(D, H), self.modes1, self.modes2, self.modes3,
                                    self.out_channels, out=out, accumulate=accumulate, addend=addend, act=act)
 
     def forward(self, x, p=None):
         if self.feature_transform:
-            raise NotImplementedError("FiLM spectral conditioning is not on the MI355X path")
+            raise NotImplementedError(self.FILM_MSG)
         B, C, D, H, W = x.shape
         ops.check_modes3d(D, H, W, self.modes1, self.modes2, self.modes3)
         if x.dtype == torch.bfloat16:  # bf16 storage (C5), inference only

@@ -171,6 +171,16 @@ _SIGS = {
     "nps_spectral_conv2d_bwd_nchw": (_i, [_vp, _l, _vp, _vp, _vp, _l, _vp, _l, _vp, _vp, _vp] + [_i] * 7 + [_vp]),
     "nps_spectral_conv3d_fwd_nchw": (_i, [_vp, _l] + [_vp] * 5 + [_l, _vp] + [_i] * 11 + [_vp]),
     "nps_spectral_conv3d_bwd_nchw": (_i, [_vp, _l] + [_vp] * 5 + [_l, _vp, _l] + [_vp] * 5 + [_i] * 9 + [_vp]),
+    # FiLM conditioning of SpectralConv2d: stages and one-call composites
+    "nps_spectral_film_scale": (_i, [_vp] * 4 + [_i] * 7 + [_vp]),
+    "nps_spectral_mix_scaled": (_i, [_vp] * 4 + [_i] * 5 + [_vp]),
+    "nps_spectral_film_bwd": (_i, [_vp] * 4 + [_i] * 4 + [_vp]),
+    "nps_spectral_film_param_bwd": (_i, [_vp] * 6 + [_i] * 7 + [_vp]),
+    "nps_spectral_conv2d_film_workspace": (_sz, [_i] * 7),
+    "nps_spectral_conv2d_film_fwd": (_i, [_vp] * 8 + [_i] * 11 + [_vp]),
+    "nps_spectral_conv2d_film_bwd": (_i, [_vp] * 14 + [_i] * 9 + [_vp]),
+    "nps_spectral_conv2d_film_fwd_nchw": (_i, [_vp, _l] + [_vp] * 6 + [_l, _vp] + [_i] * 11 + [_vp]),
+    "nps_spectral_conv2d_film_bwd_nchw": (_i, [_vp, _l] + [_vp] * 6 + [_l, _vp, _l] + [_vp] * 6 + [_i] * 9 + [_vp]),
     # bf16 storage (C5)
     "nps_spectral_dft_w_bf16": (_i, [ctypes.POINTER(Src), _i, _i, _i, _i, _i, _i, _vp, _vp]),
     "nps_spectral_mix_bf16": (_i, [_vp, _vp, _vp, _i, _i, _i, _i, _i, _vp]),

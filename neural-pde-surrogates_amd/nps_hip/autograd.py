@@ -755,6 +755,144 @@ def spectral_conv2d_nchw(module, x):
                                       module.weights2, module.packed(H))
 
 
+def _film_bwd_mid(ctx, gZ):
+    """The layout-independent middle of the FiLM SpectralConv2d backward: gZ (the W pass's adjoint of gy) ->
+    (gX2, gwp, dp, dWf, dbf).  The unscaled mixer output is formed again from the saved X2 (never Y / S)."""
+    m1, m2, Cout, mode = ctx.meta
+    B, H, W, Cin = ctx.shape
+    X2, wpack, S, p, Wf = ctx.saved_tensors
+    R, K = X2.shape[1], p.shape[1]
+    dev = gZ.device
+    s = stream_ptr()
+    c64 = torch.complex64
+    gY = torch.empty((B, R, m2, Cout), dtype=c64, device=dev)
+    Yu = torch.empty((B, R, m2, Cout), dtype=c64, device=dev)
+    gS = torch.empty((B, R, m2, Cout), dtype=torch.float32, device=dev)
+    gX2 = torch.empty((B, R, m2, Cin), dtype=c64, device=dev)
+    gwp = torch.empty((R, m2, Cin, Cout), dtype=c64, device=dev)
+    check(lib.nps_spectral_dft_h(ptr(gZ), ptr(gY), B, H, m1, m2, Cout, s), "spectral_dft_h (bwd)")
+    check(lib.nps_spectral_mix(ptr(X2), ptr(wpack), ptr(Yu), B, R, m2, Cin, Cout, s), "spectral_mix (bwd)")
+    check(lib.nps_spectral_film_bwd(ptr(Yu), ptr(S), ptr(gY), ptr(gS), B, R, m2, Cout, s), "spectral_film_bwd")
+    need = ctx.needs_input_grad[5:8]
+    dp = torch.empty_like(p) if need[0] else None
+    dWf = torch.empty_like(Wf) if need[1] else None
+    dbf = torch.empty((Wf.shape[0],), dtype=torch.float32, device=dev) if need[2] else None
+    if any(need):
+        check(lib.nps_spectral_film_param_bwd(ptr(gS), ptr(p), ptr(Wf), ptr(dWf), ptr(dbf), ptr(dp), B, K, Cout, H,
+                                              m1, m2, mode, s), "spectral_film_param_bwd")
+    check(lib.nps_spectral_mix_bwd(ptr(X2), ptr(wpack), ptr(gY), ptr(gX2), ptr(gwp), B, R, m2, Cin, Cout, s),
+          "spectral_mix_bwd")
+    return gX2, gwp, dp, dWf, dbf
+
+
+def _film_unpack(ctx, gwp, dev):
+    m1, m2, Cout, _ = ctx.meta
+    B, H, W, Cin = ctx.shape
+    dw1 = torch.empty((Cin, Cout, m1, m2), dtype=torch.complex64, device=dev)
+    dw2 = torch.empty((Cin, Cout, m1, m2), dtype=torch.complex64, device=dev)
+    check(lib.nps_spectral_unpack_grad(ptr(gwp), ptr(dw1), ptr(dw2), Cin, Cout, H, m1, m2, stream_ptr()),
+          "spectral_unpack_grad")
+    return dw1, dw2
+
+
+class SpectralConv2dFilmFn(torch.autograd.Function):
+    """SpectralConv2d.forward with FiLM conditioning (proc_fno.py:257-288 with :271-284), NHWC: the mixed modes
+    times the real factor S (ops.film_scale) of p (B, K) and weights_feat; gradients for x, weights1/2, p and
+    weights_feat's weight and bias."""
+
+    @staticmethod
+    def forward(ctx, meta, x, w1, w2, wpack, p, Wf, bf):
+        m1, m2, Cout, mode = meta
+        x = _c(x)
+        B, H, W, Cin = x.shape
+        p, Wf, bf = _c(p), _c(Wf), _c(bf)
+        dev = x.device
+        X1 = torch.empty((B, H, m2, Cin), dtype=torch.complex64, device=dev)
+        y = ops.empty_nhwc(B, H, W, Cout, x)
+        s = stream_ptr()
+        check(lib.nps_spectral_dft_w(ops._c_src([Src(x)]), 1, B, H, W, Cin, m2, ptr(X1), s), "spectral_dft_w")
+        X2, Z, S = ops.spectral_mid2d(X1, wpack, B, H, m1, m2, Cin, Cout, film=(p, Wf, bf, mode))
+        check(lib.nps_spectral_idft_w(ptr(Z), ptr(y), B, H, W, m2, Cout, 0, None, 0, ops.new_tag(y), s),
+              "spectral_idft_w")
+        ctx.meta, ctx.shape = meta, (B, H, W, Cin)
+        ctx.save_for_backward(X2, wpack, S, p, Wf)
+        return y
+
+    @staticmethod
+    def backward(ctx, gy):
+        m1, m2, Cout, _ = ctx.meta
+        B, H, W, Cin = ctx.shape
+        gy = _c(gy)
+        dev = gy.device
+        s = stream_ptr()
+        gZ = torch.empty((B, H, m2, Cout), dtype=torch.complex64, device=dev)
+        check(lib.nps_spectral_idft_w_bwd(ptr(gy), ptr(gZ), B, H, W, m2, Cout, s), "spectral_idft_w_bwd")
+        gX2, gwp, dp, dWf, dbf = _film_bwd_mid(ctx, gZ)
+        dx = dw1 = dw2 = None
+        if ctx.needs_input_grad[1]:
+            gX1 = torch.empty((B, H, m2, Cin), dtype=torch.complex64, device=dev)
+            check(lib.nps_spectral_idft_h(ptr(gX2), ptr(gX1), B, H, m1, m2, Cin, s), "spectral_idft_h (bwd)")
+            dx = torch.empty((B, H, W, Cin), dtype=torch.float32, device=dev)
+            check(lib.nps_spectral_dft_w_bwd(ptr(gX1), ptr(dx), B, H, W, m2, Cin, s), "spectral_dft_w_bwd")
+        if ctx.needs_input_grad[2] or ctx.needs_input_grad[3]:
+            dw1, dw2 = _film_unpack(ctx, gwp, dev)
+        return None, dx, dw1, dw2, None, dp, dWf, dbf
+
+
+class SpectralConv2dFilmNchwFn(torch.autograd.Function):
+    """SpectralConv2dFilmFn on the module's own NCHW tensors (as SpectralConv2dNchwFn: no transposes)."""
+
+    @staticmethod
+    def forward(ctx, meta, x, w1, w2, wpack, p, Wf, bf):
+        m1, m2, Cout, mode = meta
+        x, x_bs = ops.channels_first(x)
+        B, Cin, H, W = x.shape
+        p, Wf, bf = _c(p), _c(Wf), _c(bf)
+        y = torch.empty((B, Cout, H, W), dtype=torch.float32, device=x.device)
+        X2, S = ops.spectral_conv2d_nchw_stages(x, x_bs, wpack, m1, m2, Cout, y, 0, film=(p, Wf, bf, mode))
+        ctx.meta, ctx.shape = meta, (B, H, W, Cin)
+        ctx.save_for_backward(X2, wpack, S, p, Wf)
+        return y
+
+    @staticmethod
+    def backward(ctx, gy):
+        m1, m2, Cout, _ = ctx.meta
+        B, H, W, Cin = ctx.shape
+        gy, gy_bs = ops.channels_first(gy)
+        dev = gy.device
+        s = stream_ptr()
+        gZ = torch.empty((B, H, m2, Cout), dtype=torch.complex64, device=dev)
+        check(lib.nps_spectral_idft_w_bwd_nchw(ptr(gy), gy_bs, ptr(gZ), B, H, W, m2, Cout, s),
+              "spectral_idft_w_bwd_nchw")
+        gX2, gwp, dp, dWf, dbf = _film_bwd_mid(ctx, gZ)
+        dx = dw1 = dw2 = None
+        if ctx.needs_input_grad[1]:
+            gX1 = torch.empty((B, H, m2, Cin), dtype=torch.complex64, device=dev)
+            check(lib.nps_spectral_idft_h(ptr(gX2), ptr(gX1), B, H, m1, m2, Cin, s), "spectral_idft_h (bwd)")
+            dx = torch.empty((B, Cin, H, W), dtype=torch.float32, device=dev)
+            check(lib.nps_spectral_dft_w_bwd_nchw(ptr(gX1), ptr(dx), 0, B, H, W, m2, Cin, s),
+                  "spectral_dft_w_bwd_nchw")
+        if ctx.needs_input_grad[2] or ctx.needs_input_grad[3]:
+            dw1, dw2 = _film_unpack(ctx, gwp, dev)
+        return None, dx, dw1, dw2, None, dp, dWf, dbf
+
+
+def _film_args(module, p, H):
+    assert p is not None  # proc_fno.py:272: we must have supplied params
+    return ((module.modes1, module.modes2, module.out_channels, int(module.transform_mode)), module.weights1,
+            module.weights2, module.packed(H), p, module.weights_feat.weight, module.weights_feat.bias)
+
+
+def spectral_conv2d_film(module, x, p):
+    meta, *rest = _film_args(module, p, x.shape[1])
+    return SpectralConv2dFilmFn.apply(meta, x, *rest)
+
+
+def spectral_conv2d_film_nchw(module, x, p):
+    meta, *rest = _film_args(module, p, x.shape[2])
+    return SpectralConv2dFilmNchwFn.apply(meta, x, *rest)
+
+
 class SpectralConv3dNchwFn(torch.autograd.Function):
     """SpectralConv3dFn on the module's own NCDHW tensors: x (B, Cin, D, H, W) -> (B, Cout, D, H, W), gy read and
     dx written channels-first; the saved tensors are the same X3 and wpack."""

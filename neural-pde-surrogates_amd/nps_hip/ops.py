@@ -763,10 +763,40 @@ def ctypes_byref(x):
 
 
 # --------------------------------------------------------------- spectral -----
-def spectral_z(srcs: Sequence[Src], wpack: torch.Tensor, m1: int, m2: int, Cout: int) -> torch.Tensor:
+def film_scale(film, B: int, Cout: int, H: int, m1: int, m2: int) -> torch.Tensor:
+    """The FiLM factor S (B, R, m2, Cout) fp32 of the retained modes (proc_fno.py:271-284; include/nps.h,
+    nps_spectral_film_scale) from film = (p (B, K), weights_feat.weight (Cout*2*m1*m2, K), weights_feat.bias,
+    transform_mode)."""
+    p, Wf, bf, mode = film
+    for t in (p, Wf, bf):
+        ptr(t)  # no CPU path
+        if t.dtype != torch.float32:
+            raise TypeError(f"FiLM operands are fp32 tensors, got {t.dtype}")
+    N = Cout * 2 * m1 * m2
+    if p.dim() != 2 or p.shape[0] != B or tuple(Wf.shape) != (N, p.shape[1]) or tuple(bf.shape) != (N,):
+        raise ValueError(f"FiLM shapes: p (B={B}, K), weights_feat.weight ({N}, K), bias ({N},); got "
+                         f"{tuple(p.shape)}, {tuple(Wf.shape)}, {tuple(bf.shape)}")
+    p, Wf, bf = p.detach().contiguous(), Wf.detach().contiguous(), bf.detach().contiguous()
+    S = torch.empty((B, min(H, 2 * m1), m2, Cout), dtype=torch.float32, device=p.device)
+    check(lib.nps_spectral_film_scale(ptr(p), ptr(Wf), ptr(bf), ptr(S), B, p.shape[1], Cout, H, m1, m2, int(mode),
+                                      stream_ptr()), "spectral_film_scale")
+    return S
+
+
+def spectral_mix(X2, wpack, Y, B, R, m2, Cin, Cout, S=None):
+    """Y = the per-mode channel mixing of X2 (times the FiLM factor S in the store, when given)."""
+    if S is None:
+        check(lib.nps_spectral_mix(ptr(X2), ptr(wpack), ptr(Y), B, R, m2, Cin, Cout, stream_ptr()), "spectral_mix")
+    else:
+        check(lib.nps_spectral_mix_scaled(ptr(X2), ptr(wpack), ptr(S), ptr(Y), B, R, m2, Cin, Cout, stream_ptr()),
+              "spectral_mix_scaled")
+
+
+def spectral_z(srcs: Sequence[Src], wpack: torch.Tensor, m1: int, m2: int, Cout: int, film=None) -> torch.Tensor:
     """Z (B, H, m2, Cout) complex64: the spectral conv up to its W-pass synthesis (rfft2 W and H passes on the
     retained modes, the mode mixing, the inverse H pass; proc_fno.py:257-288) — spectral_conv2d's idft_w input, or the
-    spec_z a 1x1 conv's epilogue synthesises itself (conv2d(spec=...), the FNO layer fusion)."""
+    spec_z a 1x1 conv's epilogue synthesises itself (conv2d(spec=...), the FNO layer fusion).  film = (p, Wf, bf,
+    transform_mode): FiLM conditioning of the mixed modes (film_scale)."""
     t0 = srcs[0].t
     B, H, W = t0.shape[0], t0.shape[1], t0.shape[2]
     Cin = sum(s.t.shape[3] for s in srcs)
@@ -778,10 +808,11 @@ def spectral_z(srcs: Sequence[Src], wpack: torch.Tensor, m1: int, m2: int, Cout:
     X2 = torch.empty((B, R, m2, Cin), dtype=torch.complex64, device=dev)
     Y = torch.empty((B, R, m2, Cout), dtype=torch.complex64, device=dev)
     Z = torch.empty((B, H, m2, Cout), dtype=torch.complex64, device=dev)
+    S = film_scale(film, B, Cout, H, m1, m2) if film is not None else None
     s = stream_ptr()
     check(lib.nps_spectral_dft_w(_c_src(srcs), len(srcs), B, H, W, Cin, m2, ptr(X1), s), "spectral_dft_w")
     check(lib.nps_spectral_dft_h(ptr(X1), ptr(X2), B, H, m1, m2, Cin, s), "spectral_dft_h")
-    check(lib.nps_spectral_mix(ptr(X2), ptr(wpack), ptr(Y), B, R, m2, Cin, Cout, s), "spectral_mix")
+    spectral_mix(X2, wpack, Y, B, R, m2, Cin, Cout, S)
     check(lib.nps_spectral_idft_h(ptr(Y), ptr(Z), B, H, m1, m2, Cout, s), "spectral_idft_h")
     return Z
 
@@ -798,11 +829,11 @@ def spectral_fusable(W: int, m2: int, Cout: int) -> bool:
 
 
 def spectral_conv2d(srcs: Sequence[Src], wpack: torch.Tensor, m1: int, m2: int, Cout: int,
-                    out: Optional[torch.Tensor] = None, accumulate=False, addend=None, act=0):
-    """y = irfft2(P(rfft2(x))) on the retained modes (proc_fno.py:257-288), NHWC in/out."""
+                    out: Optional[torch.Tensor] = None, accumulate=False, addend=None, act=0, film=None):
+    """y = irfft2(P(rfft2(x))) on the retained modes (proc_fno.py:257-288), NHWC in/out; film as in spectral_z."""
     t0 = srcs[0].t
     B, H, W = t0.shape[0], t0.shape[1], t0.shape[2]
-    Z = spectral_z(srcs, wpack, m1, m2, Cout)
+    Z = spectral_z(srcs, wpack, m1, m2, Cout, film=film)
     if out is not None:
         drop_stats(out)
     if out is None:
@@ -901,42 +932,46 @@ def _out_channels_first(out, shape, like):
     return out, obs, True
 
 
-def spectral_mid2d(X1, wpack, B, H, m1, m2, Cin, Cout):
-    """The layout-independent middle of SpectralConv2d: X1 -> (X2 kept for the backward, Z)."""
+def spectral_mid2d(X1, wpack, B, H, m1, m2, Cin, Cout, film=None):
+    """The layout-independent middle of SpectralConv2d: X1 -> (X2 kept for the backward, Z), or with film = (p, Wf,
+    bf, transform_mode) -> (X2, Z, S): the FiLM factor S (film_scale) multiplies the mixed modes and is kept too."""
     R = min(H, 2 * m1)
     dev = X1.device
     X2 = torch.empty((B, R, m2, Cin), dtype=torch.complex64, device=dev)
     Y = torch.empty((B, R, m2, Cout), dtype=torch.complex64, device=dev)
     Z = torch.empty((B, H, m2, Cout), dtype=torch.complex64, device=dev)
+    S = film_scale(film, B, Cout, H, m1, m2) if film is not None else None
     s = stream_ptr()
     check(lib.nps_spectral_dft_h(ptr(X1), ptr(X2), B, H, m1, m2, Cin, s), "spectral_dft_h")
-    check(lib.nps_spectral_mix(ptr(X2), ptr(wpack), ptr(Y), B, R, m2, Cin, Cout, s), "spectral_mix")
+    spectral_mix(X2, wpack, Y, B, R, m2, Cin, Cout, S)
     check(lib.nps_spectral_idft_h(ptr(Y), ptr(Z), B, H, m1, m2, Cout, s), "spectral_idft_h")
-    return X2, Z
+    return (X2, Z) if film is None else (X2, Z, S)
 
 
-def spectral_conv2d_nchw_stages(x, x_bs, wpack, m1, m2, Cout, out, out_bs, accumulate=False, act=0):
-    """SpectralConv2d forward chain reading x and writing out channels-first.  Returns X2 (kept for the backward)."""
+def spectral_conv2d_nchw_stages(x, x_bs, wpack, m1, m2, Cout, out, out_bs, accumulate=False, act=0, film=None):
+    """SpectralConv2d forward chain reading x and writing out channels-first.  Returns X2 (kept for the backward), or
+    (X2, S) with film (spectral_mid2d)."""
     B, Cin, H, W = x.shape
     if not (m1 <= H and m2 <= W // 2 + 1):
         raise AssertionError("modes should be at most the spatial dim (// 2 + 1 for the last spatial dimension)")
     X1 = torch.empty((B, H, m2, Cin), dtype=torch.complex64, device=x.device)
     s = stream_ptr()
     check(lib.nps_spectral_dft_w_nchw(ptr(x), x_bs, B, H, W, Cin, m2, ptr(X1), s), "spectral_dft_w_nchw")
-    X2, Z = spectral_mid2d(X1, wpack, B, H, m1, m2, Cin, Cout)
+    X2, Z, *S = spectral_mid2d(X1, wpack, B, H, m1, m2, Cin, Cout, film=film)
     check(lib.nps_spectral_idft_w_nchw(ptr(Z), ptr(out), out_bs, B, H, W, m2, Cout, 1 if accumulate else 0, act, s),
           "spectral_idft_w_nchw")
-    return X2
+    return X2 if film is None else (X2, S[0])
 
 
 def spectral_conv2d_nchw(x: torch.Tensor, wpack: torch.Tensor, m1: int, m2: int, Cout: int,
-                         out: Optional[torch.Tensor] = None, accumulate=False, act=0):
+                         out: Optional[torch.Tensor] = None, accumulate=False, act=0, film=None):
     """y = irfft2(P(rfft2(x))) on the retained modes (proc_fno.py:257-288), NCHW in / out with no transpose: x
-    (B, Cin, H, W) -> (B, Cout, H, W); out (= or +=, then act) may be a channel slice of a larger tensor."""
+    (B, Cin, H, W) -> (B, Cout, H, W); out (= or +=, then act) may be a channel slice of a larger tensor; film as in
+    spectral_z."""
     x, x_bs = channels_first(x)
     B, _, H, W = x.shape
     out, out_bs, given = _out_channels_first(out, (B, Cout, H, W), x)
-    spectral_conv2d_nchw_stages(x, x_bs, wpack, m1, m2, Cout, out, out_bs, accumulate and given, act)
+    spectral_conv2d_nchw_stages(x, x_bs, wpack, m1, m2, Cout, out, out_bs, accumulate and given, act, film=film)
     return out
 
 
