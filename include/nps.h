@@ -374,6 +374,58 @@ int nps_spectral_conv2d_film_bwd_nchw(const float* x, long x_bs, const float* w1
                                       void* ws, int B, int Cin, int Cout, int H, int W, int m1, int m2, int K,
                                       int transform_mode, void* stream);
 
+/* ---- SpectralConv1d / FNO-1D (proc_fno.py:158-222) ----------------------------------------------------
+ * Channels-last activations (B, L, C); weights1 [Cin][Cout][m] complex64; m <= L / 2 + 1.
+ *  X[B][m][C]   = sum_l x e^{-2 pi i k l / L}                     (nps_spectral1d_dft)
+ *  Y[B][m][Co]  = sum_i X * W[i][o][k]  (* S with FiLM)            (nps_spectral_mix / _mix_scaled, R = 1, m2 = m)
+ *  y[B][L][Co]  = c2r_L(Y) / L  (+ epilogue)                       (nps_spectral1d_idft)
+ * Both transforms split L over work-groups; the analysis adds a work-group's sub-chunks in ascending order in
+ * LDS and the work-groups' partials in ascending order in a second kernel (no atomics: bit-repeatable).  Envelope: 1 <= B <= 65535, C >= 1, 2 <= L <= 65536,
+ * 1 <= m <= min(L / 2 + 1, 128); anything else is an error (-1, text in nps_last_error) before any launch.
+ *
+ * dft: `src` as for nps_spectral_dft_w with H = 1, W = L (up to NPS_MAX_SRC sources, any channel counts; 16-B
+ * loads when every source has C % 4 == 0); ws: nps_spectral1d_dft_workspace(B, L, C, m) bytes of device memory
+ * (0 = bad shape) for the partials.  adjoint != 0: every bin scaled by c_k / L (c_k = 1 for DC and the Nyquist
+ * bin of an even L, else 2), the adjoint of nps_spectral1d_idft's synthesis (gy -> gY). */
+size_t nps_spectral1d_dft_workspace(int B, int L, int C, int m);
+int nps_spectral1d_dft(const nps_src_t* src, int nsrc, int B, int L, int C, int m, float* X, float* ws, int adjoint,
+                       void* stream);
+/* idft: out[B][L][Cout] (= or +=) act(y + addend), accumulate / addend / act as for nps_spectral_idft_w.
+ * adjoint != 0: no doubling and no 1 / L, gx[l] = sum_k Re(gX_k e^{+2 pi i k l / L}), the adjoint of the analysis. */
+int nps_spectral1d_idft(const float* Z, float* out, int B, int L, int m, int Cout, int accumulate, const float* addend,
+                        int act, int adjoint, void* stream);
+/* wpack [m][Cin][Cout] complex (the mixer's layout with R = 1) from weights1 [Cin][Cout][m], and the adjoint */
+int nps_spectral1d_pack_weights(const float* w, float* wpack, int Cin, int Cout, int m, void* stream);
+int nps_spectral1d_unpack_grad(const float* gwpack, float* gw, int Cin, int Cout, int m, void* stream);
+/* nps_spectral_mix_bwd (R = 1, m2 = m) at any batch size: runs of 32 samples, each run's weight gradient into its
+ * own part of gwpack [nps_spectral1d_mix_bwd_parts(B)][m][Cin][Cout], then the parts added into part 0 in ascending
+ * order (the result; the other parts are scratch). */
+int nps_spectral1d_mix_bwd_parts(int B);
+int nps_spectral1d_mix_bwd(const float* X, const float* wpack, const float* gY, float* gX, float* gwpack, int B, int m,
+                           int Cin, int Cout, void* stream);
+/* FiLM (proc_fno.py:209-218): F[b][n] = bias[n] + sum_k p[b][k] wf[n][k], n = o * m + k (.view(B, Cout, m), no
+ * factor 2); S[B][m][Cout] = 1 + F (transform_mode 0) or F (1).  K in [1, 64].  nps_spectral_film_bwd (R = 1) gives
+ * gS; param_bwd: gwf [N][K], gbias [N], gp [B][K], each written or NULL = skipped, fp64 sums in a fixed order. */
+int nps_spectral1d_film_scale(const float* p, const float* wf, const float* bias, float* S, int B, int K, int Cout,
+                              int m, int transform_mode, void* stream);
+int nps_spectral1d_film_param_bwd(const float* gS, const float* p, const float* wf, float* gwf, float* gbias,
+                                  float* gp, int B, int K, int Cout, int m, int transform_mode, void* stream);
+/* One call per module, as nps_spectral_conv2d_*: x / y / dy / dx fp32 [B][L][C], w / dw the complex64 nn.Parameter
+ * [Cin][Cout][m], ws >= the *_workspace() bytes (forward and backward alike; 0 = bad shape); dx, dw, dp, dwf,
+ * dbias: written, each NULL = skipped. */
+size_t nps_spectral_conv1d_workspace(int B, int Cin, int Cout, int L, int m);
+int nps_spectral_conv1d_fwd(const float* x, const float* w, float* y, void* ws, int B, int Cin, int Cout, int L, int m,
+                            int accumulate, int act, void* stream);
+int nps_spectral_conv1d_bwd(const float* x, const float* w, const float* dy, float* dx, float* dw, void* ws, int B,
+                            int Cin, int Cout, int L, int m, void* stream);
+size_t nps_spectral_conv1d_film_workspace(int B, int Cin, int Cout, int L, int m);
+int nps_spectral_conv1d_film_fwd(const float* x, const float* w, const float* p, const float* wf, const float* bias,
+                                 float* y, void* ws, int B, int Cin, int Cout, int L, int m, int K, int transform_mode,
+                                 int accumulate, int act, void* stream);
+int nps_spectral_conv1d_film_bwd(const float* x, const float* w, const float* p, const float* wf, const float* bias,
+                                 const float* dy, float* dx, float* dw, float* dp, float* dwf, float* dbias, void* ws,
+                                 int B, int Cin, int Cout, int L, int m, int K, int transform_mode, void* stream);
+
 /* ---- bf16 storage (BASELINE config C5: the 3-D rFFT spectral conv in bf16) ----------------------------
  * Activations in HBM as bf16 (16-bit storage of NDHWC tensors viewed as (B, D*H, W, C)), every sum in fp32:
  * the same transforms as the fp32 entry points above.  Replaces the fp32 SpectralConv3d / FNO_Layer chain of

@@ -288,10 +288,39 @@ class Conv3d(_Packed3Mixin, _PackedMixin, nn.Conv3d):
         return y.reshape(B, self.out_channels, D, H, W)
 
 
+class Conv1d(_PackedMixin, nn.Conv1d):
+    """nn.Conv1d parameters (common.py:37-47 with spatial_dim 1).  The FNO-1D pointwise `w` conv (fno_kernel_size 1)
+    runs as a 1x1 conv over the (B, 1, L, C) view of channels-last activations on the 2-D HIP conv kernels
+    (run / run_ad); every other geometry keeps nn.Conv1d's own forward."""
+
+    def pointwise(self):
+        return (tuple(self.kernel_size) == (1,) and tuple(self.stride) == (1,) and tuple(self.dilation) == (1,)
+                and self.groups == 1)
+
+    def _check(self):
+        if not self.pointwise():
+            raise NotImplementedError("only pointwise (kernel 1) 1-D convs run on the MI355X path")
+
+    def geometry(self):
+        return 1, 1, 1, 1, (0, 0), (0, 0), 0
+
+    def run(self, srcs, frame_hw, **kw):
+        """srcs: (B, L, C) sources viewed as (B, 1, L, C); frame_hw = (1, L)."""
+        self._check()
+        pk = self._packed(lambda w: ops.pack_conv_weight(w.reshape(w.shape[0], w.shape[1], 1, 1)), "conv1d")
+        return ops.conv2d(srcs, frame_hw, pk, self.bias, self.out_channels, 1, 1, **kw)
+
+    def run_ad(self, x):
+        """Differentiable form: x (B, 1, L, Cin)."""
+        self._check()
+        return ad.Conv2dFn.apply(self.geometry(), x, self.weight.reshape(self.out_channels, self.in_channels, 1, 1),
+                                 self.bias)
+
+
 def get_conv_with_right_spatial_dim(spatial_dim, **kwargs):
     """common.py:37-47."""
     if spatial_dim == 1:
-        return nn.Conv1d(**kwargs)
+        return Conv1d(**kwargs)
     if spatial_dim == 2:
         return Conv2d(**kwargs)
     if spatial_dim == 3:

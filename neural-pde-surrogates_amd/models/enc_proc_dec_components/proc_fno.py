@@ -2,8 +2,9 @@
 
 Same classes, constructor kwargs and parameters (weights1/weights2 complex64
 (Cin, Cout, m1, m2)) as the reference; forward runs the truncated-DFT HIP
-pipeline (nps_hip.ops.spectral_conv2d).  Internal entry points `run(...)` take
-NHWC tensors / virtual frames so composite models never transpose.
+pipeline (nps_hip.ops.spectral_conv2d; 1-D: ops.spectral_conv1d).  Internal
+entry points `run(...)` take NHWC tensors / virtual frames so composite models
+never transpose.
 """
 import torch
 from torch import nn
@@ -48,9 +49,9 @@ class FNO(nn.Module):
         """The layers' FiLM operand: `variables` (B, n_cond) for cond_mode "film" with n_cond > 0, else None."""
         if self.cond_mode != "film" or not self.fno_layers[0].conv.feature_transform:
             return None  # film with n_cond == 0 is a plain FNO
-        if self.num_spatial_dims != 2:
+        if self.num_spatial_dims not in (1, 2):
             raise NotImplementedError(SpectralConv3d.FILM_MSG if self.num_spatial_dims == 3 else
-                                      "FiLM conditioning is on the MI355X path for 2-D FNOs only")
+                                      "FiLM conditioning is on the MI355X path for 1-D and 2-D FNOs only")
         if variables is None:
             raise NotImplementedError(
                 "FNO(cond_mode='film') needs `variables` (B, n_cond): call forward(h, variables=...).  The reference "
@@ -59,8 +60,8 @@ class FNO(nn.Module):
         return variables
 
     def run(self, h, vb, D=None, variables=None):
-        """NHWC: h (B,H,W,C), vb (B,H,W,K) or None (3-D: NDHWC viewed as (B, D*H, W, C), depth D); variables (B,
-        n_cond): the FiLM operand of cond_mode "film"."""
+        """NHWC: h (B,H,W,C), vb (B,H,W,K) or None (3-D: NDHWC viewed as (B, D*H, W, C), depth D; 1-D: channels-last
+        (B, L, C) viewed as (B, 1, L, C)); variables (B, n_cond): the FiLM operand of cond_mode "film"."""
         p = self._film_p(variables)
         for layer in self.fno_layers:
             srcs = [ops.Src(h)] + ([ops.Src(vb)] if (vb is not None and self.cond_mode == "concat") else [])
@@ -90,6 +91,11 @@ class FNO(nn.Module):
     def forward(self, h: torch.Tensor, variables: torch.Tensor = None, variables_broadcast: torch.Tensor = None,
                 pos=None):
         self._film_p(variables)  # a FiLM FNO without `variables`, or in 3-D, raises before any work
+        if self.num_spatial_dims == 1:  # (B, C, L): the layers run on the (B, 1, L, C) view
+            for layer in self.fno_layers:
+                layer._check_1d()  # fno_kernel_size > 1 raises before any work
+            one = lambda t: t.unsqueeze(2) if t is not None else None
+            return self.forward2d(one(h), variables, one(variables_broadcast)).squeeze(2)
         if self.num_spatial_dims == 3:  # (B, C, D, H, W): the layers run on the (B, D*H, W, C) view
             B, C, D, H, W = h.shape
             flat = lambda t: t.reshape(t.shape[0], t.shape[1], D * H, W)
@@ -109,6 +115,10 @@ class FNO(nn.Module):
                 vb = ops.nchw_to_nhwc(flat(variables_broadcast)) if variables_broadcast is not None else None
                 y = ops.nhwc_to_nchw(self.run(ops.nchw_to_nhwc(flat(h)), vb, D))
             return y.reshape(B, y.shape[1], D, H, W)
+        return self.forward2d(h, variables, variables_broadcast)
+
+    def forward2d(self, h, variables, variables_broadcast):
+        """(B, C, H, W) tensors through the NHWC layers (H = 1: the 1-D FNO's (B, C, 1, L) view)."""
         if use_autograd(self):
             vb = ad.to_nhwc(variables_broadcast) if variables_broadcast is not None else None
             return ad.to_nchw(self.run_ad(ad.to_nhwc(h), vb, variables=variables))
@@ -159,9 +169,15 @@ class FNO_Layer(nn.Module):
             else:
                 assert self.modes[i] <= s, 'modes should be at most the spatial dim all but the last spatial dimensions!'
 
+    def _check_1d(self):
+        if any(tuple(c.kernel_size) != (1,) for c in (self.w, getattr(self, "w2", self.w))):
+            raise NotImplementedError("FNO_Layer 1-D: fno_kernel_size > 1 is not on the MI355X path (pointwise `w` "
+                                      "convs only)")
+
     def run(self, srcs, act_override=None, D=None, p=None):
         """srcs: virtual NHWC input frame (h, vb) — for 3-D layers NDHWC sources viewed as (B, D*H, W, C); p (B, K):
-        the FiLM operand of a 2-D layer with feature_transform.  Returns act(spectral(x) + w(x) [+ w2(x)])."""
+        the FiLM operand of a 1-D / 2-D layer with feature_transform (1-D layers: (B, 1, L, C) views).  Returns
+        act(spectral(x) + w(x) [+ w2(x)])."""
         if self.num_spatial_dims == 3:
             DH, W = srcs[0].t.shape[1:3]
             self._check_modes((D, DH // D, W))
@@ -170,8 +186,22 @@ class FNO_Layer(nn.Module):
             act = activation_code(self.act) if act_override is None else act_override
             out = self.w.run(srcs, (DH, W))
             return self.conv.run(srcs, D, out=out, accumulate=True, act=act)
-        if self.num_spatial_dims != 2:
-            raise NotImplementedError("FNO_Layer: 2-D / 3-D only on the MI355X path")
+        if self.num_spatial_dims == 1:
+            one, L = srcs[0].t.shape[1:3]
+            assert one == 1, "1-D layers take channels-last (B, L, C) sources viewed as (B, 1, L, C)"
+            self._check_modes((L,))
+            self._check_1d()
+            act = activation_code(self.act) if act_override is None else act_override
+            # a pointwise conv does not care how its pixels are arranged: 32-point rows fill the 2-D conv tiles that
+            # a 1 x L image would leave 1/8 .. 1/32 used
+            rows = L // 32 if (L % 32 == 0 and all(s.off_y == 0 and s.off_x == 0 for s in srcs)) else 1
+            fold = lambda t: ops.share_tag(t.view(t.shape[0], rows, L // rows, t.shape[3]), t)
+            psrcs = [ops.Src(fold(s.t)) for s in srcs] if rows > 1 else srcs
+            out = self.w.run(psrcs, (rows, L // rows))
+            if self.conv_mode == "double":
+                self.w2.run(psrcs, (rows, L // rows), out=out, accumulate=True)
+            out = out.view(out.shape[0], 1, L, out.shape[3])
+            return self.conv.run(srcs, out=out, accumulate=True, act=act, p=p)
         H, W = srcs[0].t.shape[1:3]
         self._check_modes((H, W))
         act = activation_code(self.act) if act_override is None else act_override
@@ -205,8 +235,16 @@ class FNO_Layer(nn.Module):
                 raise NotImplementedError("FNO_Layer 3-D: conv_mode 'single' only on the MI355X path")
             y = ad.add_at(ad.spectral_conv3d(self.conv, x, D), self.w.run_ad(x))
             return ad.act(y, activation_code(self.act))
-        if self.num_spatial_dims != 2:
-            raise NotImplementedError("FNO_Layer: 2-D / 3-D only on the MI355X path")
+        if self.num_spatial_dims == 1:
+            assert x.shape[1] == 1, "1-D layers take channels-last (B, L, C) tensors viewed as (B, 1, L, C)"
+            self._check_modes(x.shape[2:3])
+            self._check_1d()
+            spec = (ad.spectral_conv1d_film(self.conv, x, p) if self.conv.feature_transform
+                    else ad.spectral_conv1d(self.conv, x))
+            y = ad.add_at(spec, self.w.run_ad(x))
+            if self.conv_mode == "double":
+                y = ad.add_at(y, self.w2.run_ad(x))
+            return ad.act(y, activation_code(self.act))
         self._check_modes(x.shape[1:3])
         spec = (ad.spectral_conv2d_film(self.conv, x, p) if self.conv.feature_transform
                 else ad.spectral_conv2d(self.conv, x))
@@ -226,10 +264,14 @@ class FNO_Layer(nn.Module):
             else:
                 y = ops.nhwc_to_nchw(self.run([ops.Src(ops.nchw_to_nhwc(x4))], D=D))
             return y.reshape(B, y.shape[1], D, H, W)
+        if self.num_spatial_dims == 1:  # (B, C, L) as (B, C, 1, L)
+            self._check_1d()
+            x = x.unsqueeze(2)
         if use_autograd(self):
-            return ad.to_nchw(self.run_ad(ad.to_nhwc(x), p=p))
-        x = ops.nchw_to_nhwc(x)
-        return ops.nhwc_to_nchw(self.run([ops.Src(x)], p=p))
+            y = ad.to_nchw(self.run_ad(ad.to_nhwc(x), p=p))
+        else:
+            y = ops.nhwc_to_nchw(self.run([ops.Src(ops.nchw_to_nhwc(x))], p=p))
+        return y.squeeze(2) if self.num_spatial_dims == 1 else y
 
 
 class SpectralConv2d(nn.Module):
@@ -292,7 +334,8 @@ class SpectralConv2d(nn.Module):
 
 
 class SpectralConv1d(nn.Module):
-    """proc_fno.py:158-222 — parameters only; not on the 2-D MI355X path."""
+    """proc_fno.py:158-222: rfft -> per-mode complex mixing of the first `modes1` bins (times the FiLM factor) ->
+    irfft, on the L-split truncated-DFT HIP kernels (include/nps.h, SpectralConv1d)."""
 
     def __init__(self, in_channels, out_channels, modes: tuple, feature_transform=False, feature_transform_dim=6,
                  transform_mode=1):
@@ -307,8 +350,40 @@ class SpectralConv1d(nn.Module):
         if feature_transform:
             self.weights_feat = nn.Linear(feature_transform_dim, self.out_channels * self.modes1)
 
+    def packed(self):
+        w = self.weights1
+        key = (w.data_ptr(), w._version, str(w.device))
+        if getattr(self, "_pk_key", None) != key:
+            self._pk = ops.pack_spectral1d_weight(w)
+            self._pk_key = key
+        return self._pk
+
+    def film(self, p):
+        """ops' FiLM operand (p, weights_feat.weight, weights_feat.bias, transform_mode); None without
+        feature_transform (p is then ignored, as in the reference)."""
+        if not self.feature_transform:
+            return None
+        assert p is not None  # proc_fno.py:210: we must have supplied params
+        return (p, self.weights_feat.weight, self.weights_feat.bias, self.transform_mode)
+
+    def run(self, srcs, out=None, accumulate=False, addend=None, act=0, p=None):
+        """srcs: channels-last (B, L, C) sources, or their (B, 1, L, C) views.  Returns (B, L, Cout), or `out`."""
+        return ops.spectral_conv1d(srcs, self.packed(), self.modes1, self.out_channels, out=out,
+                                   accumulate=accumulate, addend=addend, act=act, film=self.film(p))
+
+    def run_ad(self, x, p=None):
+        """Differentiable form on a channels-last (B, L, Cin) tensor (or its (B, 1, L, Cin) view)."""
+        return ad.spectral_conv1d_film(self, x, p) if self.feature_transform else ad.spectral_conv1d(self, x)
+
     def forward(self, x, p=None):
-        raise NotImplementedError("SpectralConv1d is not on the MI355X hot path")
+        film = self.film(p)
+        L = x.shape[2]  # x (B, C, L), transposed on the (B, C, 1, L) view by the layout kernels
+        ops.check_modes1d(L, self.modes1)
+        if use_autograd(self):
+            return ad.to_nchw(self.run_ad(ad.to_nhwc(x.unsqueeze(2)), p)).squeeze(2)
+        y = ops.spectral_conv1d([ops.Src(ops.nchw_to_nhwc(x.unsqueeze(2)))], self.packed(), self.modes1,
+                                self.out_channels, film=film)
+        return ops.nhwc_to_nchw(y.unsqueeze(1)).squeeze(2)
 
 
 class SpectralConv3d(nn.Module):

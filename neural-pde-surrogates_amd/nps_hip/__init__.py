@@ -181,6 +181,22 @@ _SIGS = {
     "nps_spectral_conv2d_film_bwd": (_i, [_vp] * 14 + [_i] * 9 + [_vp]),
     "nps_spectral_conv2d_film_fwd_nchw": (_i, [_vp, _l] + [_vp] * 6 + [_l, _vp] + [_i] * 11 + [_vp]),
     "nps_spectral_conv2d_film_bwd_nchw": (_i, [_vp, _l] + [_vp] * 6 + [_l, _vp, _l] + [_vp] * 6 + [_i] * 9 + [_vp]),
+    # SpectralConv1d / FNO-1D: transforms along L, helpers and one-call composites
+    "nps_spectral1d_dft_workspace": (_sz, [_i] * 4),
+    "nps_spectral1d_dft": (_i, [ctypes.POINTER(Src), _i, _i, _i, _i, _i, _vp, _vp, _i, _vp]),
+    "nps_spectral1d_idft": (_i, [_vp, _vp, _i, _i, _i, _i, _i, _vp, _i, _i, _vp]),
+    "nps_spectral1d_pack_weights": (_i, [_vp, _vp, _i, _i, _i, _vp]),
+    "nps_spectral1d_unpack_grad": (_i, [_vp, _vp, _i, _i, _i, _vp]),
+    "nps_spectral1d_mix_bwd_parts": (_i, [_i]),
+    "nps_spectral1d_mix_bwd": (_i, [_vp] * 5 + [_i] * 4 + [_vp]),
+    "nps_spectral1d_film_scale": (_i, [_vp] * 4 + [_i] * 5 + [_vp]),
+    "nps_spectral1d_film_param_bwd": (_i, [_vp] * 6 + [_i] * 5 + [_vp]),
+    "nps_spectral_conv1d_workspace": (_sz, [_i] * 5),
+    "nps_spectral_conv1d_fwd": (_i, [_vp] * 4 + [_i] * 7 + [_vp]),
+    "nps_spectral_conv1d_bwd": (_i, [_vp] * 6 + [_i] * 5 + [_vp]),
+    "nps_spectral_conv1d_film_workspace": (_sz, [_i] * 5),
+    "nps_spectral_conv1d_film_fwd": (_i, [_vp] * 7 + [_i] * 9 + [_vp]),
+    "nps_spectral_conv1d_film_bwd": (_i, [_vp] * 12 + [_i] * 7 + [_vp]),
     # bf16 storage (C5)
     "nps_spectral_dft_w_bf16": (_i, [ctypes.POINTER(Src), _i, _i, _i, _i, _i, _i, _vp, _vp]),
     "nps_spectral_mix_bf16": (_i, [_vp, _vp, _vp, _i, _i, _i, _i, _i, _vp]),

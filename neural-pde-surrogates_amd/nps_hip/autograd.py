@@ -893,6 +893,101 @@ def spectral_conv2d_film_nchw(module, x, p):
     return SpectralConv2dFilmNchwFn.apply(meta, x, *rest)
 
 
+# ------------------------------------------------------------------------- spectral conv, 1-D
+def _spec1d_bwd(ctx, gy, film):
+    """The SpectralConv1d backward (SURVEY.md §0.8 in one dimension): gy -> (dx, dw, dp, dWf, dbf)."""
+    m, Cout = ctx.meta[:2]
+    B, L, Cin = ctx.shape
+    X, wpack = ctx.saved_tensors[:2]
+    gy = _c(gy)
+    dev = gy.device
+    s = stream_ptr()
+    c64 = torch.complex64
+    gY = ops.spectral1d_dft([Src(gy.reshape(B, L, Cout))], m, adjoint=True)  # irfft's adjoint: c_k / L
+    dp = dWf = dbf = None
+    if film:
+        mode = ctx.meta[2]
+        S, p, Wf = ctx.saved_tensors[2:5]
+        K = p.shape[1]
+        # the unscaled mixer output again from the saved X (never Y / S: S may be zero)
+        Yu = torch.empty((B, m, Cout), dtype=c64, device=dev)
+        gS = torch.empty((B, m, Cout), dtype=torch.float32, device=dev)
+        check(lib.nps_spectral_mix(ptr(X), ptr(wpack), ptr(Yu), B, 1, m, Cin, Cout, s), "spectral_mix (bwd)")
+        check(lib.nps_spectral_film_bwd(ptr(Yu), ptr(S), ptr(gY), ptr(gS), B, 1, m, Cout, s), "spectral_film_bwd")
+        need = ctx.needs_input_grad[4:7]
+        dp = torch.empty_like(p) if need[0] else None
+        dWf = torch.empty_like(Wf) if need[1] else None
+        dbf = torch.empty((Wf.shape[0],), dtype=torch.float32, device=dev) if need[2] else None
+        if any(need):
+            check(lib.nps_spectral1d_film_param_bwd(ptr(gS), ptr(p), ptr(Wf), ptr(dWf), ptr(dbf), ptr(dp), B, K, Cout,
+                                                    m, mode, s), "spectral1d_film_param_bwd")
+    gX = torch.empty((B, m, Cin), dtype=c64, device=dev)
+    gwp = torch.empty((lib.nps_spectral1d_mix_bwd_parts(B), m, Cin, Cout), dtype=c64, device=dev)  # result: part 0
+    check(lib.nps_spectral1d_mix_bwd(ptr(X), ptr(wpack), ptr(gY), ptr(gX), ptr(gwp), B, m, Cin, Cout, s),
+          "spectral1d_mix_bwd")
+    dx = dw = None
+    if ctx.needs_input_grad[1]:
+        dx = ops.spectral1d_idft(gX, L, adjoint=True).reshape(ctx.xshape)
+    if ctx.needs_input_grad[2]:
+        dw = torch.empty((Cin, Cout, m), dtype=c64, device=dev)
+        check(lib.nps_spectral1d_unpack_grad(ptr(gwp), ptr(dw), Cin, Cout, m, s), "spectral1d_unpack_grad")
+    return dx, dw, dp, dWf, dbf
+
+
+class SpectralConv1dFn(torch.autograd.Function):
+    """SpectralConv1d.forward (proc_fno.py:199-222) on channels-last x (B, L, Cin) (or its (B, 1, L, Cin) view) and
+    its torch.fft / complex-einsum backward."""
+
+    @staticmethod
+    def forward(ctx, meta, x, w, wpack):
+        m, Cout = meta
+        x = _c(x)
+        B, L, Cin = x.shape[0], x.shape[-2], x.shape[-1]
+        X, Y, _ = ops.spectral1d_mid([Src(x)], wpack, m, Cout)
+        y = ops.spectral1d_idft(Y, L).reshape(x.shape[:-1] + (Cout,))
+        ctx.meta, ctx.shape, ctx.xshape = meta, (B, L, Cin), tuple(x.shape)
+        ctx.save_for_backward(X, wpack)
+        return y
+
+    @staticmethod
+    def backward(ctx, gy):
+        dx, dw, _, _, _ = _spec1d_bwd(ctx, gy, False)
+        return None, dx, dw, None
+
+
+class SpectralConv1dFilmFn(torch.autograd.Function):
+    """SpectralConv1dFn with FiLM conditioning (proc_fno.py:209-218): the mixed modes times the real factor S
+    (ops.film1d_scale); gradients for x, weights1, p and weights_feat's weight and bias."""
+
+    @staticmethod
+    def forward(ctx, meta, x, w, wpack, p, Wf, bf):
+        m, Cout, mode = meta
+        x = _c(x)
+        B, L, Cin = x.shape[0], x.shape[-2], x.shape[-1]
+        p, Wf, bf = _c(p), _c(Wf), _c(bf)
+        X, Y, S = ops.spectral1d_mid([Src(x)], wpack, m, Cout, film=(p, Wf, bf, mode))
+        y = ops.spectral1d_idft(Y, L).reshape(x.shape[:-1] + (Cout,))
+        ctx.meta, ctx.shape, ctx.xshape = meta, (B, L, Cin), tuple(x.shape)
+        ctx.save_for_backward(X, wpack, S, p, Wf)
+        return y
+
+    @staticmethod
+    def backward(ctx, gy):
+        dx, dw, dp, dWf, dbf = _spec1d_bwd(ctx, gy, True)
+        return None, dx, dw, None, dp, dWf, dbf
+
+
+def spectral_conv1d(module, x):
+    return SpectralConv1dFn.apply((module.modes1, module.out_channels), x, module.weights1, module.packed())
+
+
+def spectral_conv1d_film(module, x, p):
+    assert p is not None  # proc_fno.py:210: we must have supplied params
+    return SpectralConv1dFilmFn.apply((module.modes1, module.out_channels, int(module.transform_mode)), x,
+                                      module.weights1, module.packed(), p, module.weights_feat.weight,
+                                      module.weights_feat.bias)
+
+
 class SpectralConv3dNchwFn(torch.autograd.Function):
     """SpectralConv3dFn on the module's own NCDHW tensors: x (B, Cin, D, H, W) -> (B, Cout, D, H, W), gy read and
     dx written channels-first; the saved tensors are the same X3 and wpack."""

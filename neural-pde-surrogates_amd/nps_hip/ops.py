@@ -847,6 +847,105 @@ def spectral_conv2d(srcs: Sequence[Src], wpack: torch.Tensor, m1: int, m2: int, 
     return out
 
 
+# ------------------------------------------------------------ spectral, 1-D -----
+SPECTRAL1D_MAX_MODES = 128    # include/nps.h, SpectralConv1d envelope
+SPECTRAL1D_MAX_L = 65536
+
+
+def check_modes1d(L: int, m: int):
+    """The SpectralConv1d envelope (mirrors the library's host checks)."""
+    if not m <= L // 2 + 1:
+        raise AssertionError("modes should be at most the spatial dim // 2 + 1 for the last spatial dimension!")
+    if not (2 <= L <= SPECTRAL1D_MAX_L and 1 <= m <= SPECTRAL1D_MAX_MODES):
+        raise NotImplementedError(f"SpectralConv1d on the MI355X path: 2 <= L <= {SPECTRAL1D_MAX_L} and 1 <= modes <= "
+                                  f"{SPECTRAL1D_MAX_MODES}, got L={L} modes={m}")
+
+
+def pack_spectral1d_weight(w: torch.Tensor) -> torch.Tensor:
+    """weights1 (Cin, Cout, m) complex64 -> [m][Cin][Cout] complex (the mixer's packing with R = 1)."""
+    w = w.detach().contiguous()
+    Cin, Cout, m = w.shape
+    out = torch.empty((m, Cin, Cout), dtype=torch.complex64, device=w.device)
+    check(lib.nps_spectral1d_pack_weights(ptr(w), ptr(out), Cin, Cout, m, stream_ptr()), "spectral1d_pack_weights")
+    return out
+
+
+def _src1d(srcs: Sequence[Src]):
+    """(B, L, C) sources as the (B, 1, L, C) frames the C ABI takes."""
+    return _c_src([Src(s.t.unsqueeze(1) if s.t.dim() == 3 else s.t, s.off_y, s.off_x) for s in srcs])
+
+
+def spectral1d_dft(srcs: Sequence[Src], m: int, adjoint=False) -> torch.Tensor:
+    """X (B, m, C) complex64 = the first m bins of the DFT along L of the concatenated (B, L, C) sources (never
+    materialised); adjoint: scaled by c_k / L, the adjoint of spectral1d_idft's synthesis."""
+    t0 = srcs[0].t
+    B, L = t0.shape[0], t0.shape[-2]
+    C = sum(s.t.shape[-1] for s in srcs)
+    arr = _src1d(srcs)
+    check_modes1d(L, m)
+    X = torch.empty((B, m, C), dtype=torch.complex64, device=t0.device)
+    n = lib.nps_spectral1d_dft_workspace(B, L, C, m)
+    ws = torch.empty((max(n, 4) // 4,), dtype=torch.float32, device=t0.device)
+    check(lib.nps_spectral1d_dft(arr, len(srcs), B, L, C, m, ptr(X), ptr(ws), 1 if adjoint else 0, stream_ptr()),
+          "spectral1d_dft")
+    return X
+
+
+def spectral1d_idft(Z: torch.Tensor, L: int, out: Optional[torch.Tensor] = None, accumulate=False, addend=None, act=0,
+                    adjoint=False) -> torch.Tensor:
+    """out (B, L, Cout) (= or +=) act(c2r_L(Z) / L + addend) from Z (B, m, Cout) complex64; adjoint: the analysis
+    adjoint (no doubling, no 1 / L).  `out` may be any contiguous tensor of B * L * Cout floats."""
+    B, m, Cout = Z.shape
+    check_modes1d(L, m)
+    if out is None:
+        out = torch.empty((B, L, Cout), dtype=torch.float32, device=Z.device)
+        accumulate = False
+    else:
+        drop_stats(out)
+        out._nps_tag = None  # the synthesis publishes no range tag: readers measure the tensor again
+    check(lib.nps_spectral1d_idft(ptr(Z), ptr(out), B, L, m, Cout, 1 if accumulate else 0, ptr(addend), act,
+                                  1 if adjoint else 0, stream_ptr()), "spectral1d_idft")
+    return out
+
+
+def film1d_scale(film, B: int, Cout: int, m: int) -> torch.Tensor:
+    """The FiLM factor S (B, m, Cout) fp32 (proc_fno.py:209-218) from film = (p (B, K), weights_feat.weight
+    (Cout*m, K), weights_feat.bias, transform_mode)."""
+    p, Wf, bf, mode = film
+    for t in (p, Wf, bf):
+        ptr(t)  # no CPU path
+        if t.dtype != torch.float32:
+            raise TypeError(f"FiLM operands are fp32 tensors, got {t.dtype}")
+    N = Cout * m
+    if p.dim() != 2 or p.shape[0] != B or tuple(Wf.shape) != (N, p.shape[1]) or tuple(bf.shape) != (N,):
+        raise ValueError(f"FiLM shapes: p (B={B}, K), weights_feat.weight ({N}, K), bias ({N},); got "
+                         f"{tuple(p.shape)}, {tuple(Wf.shape)}, {tuple(bf.shape)}")
+    p, Wf, bf = p.detach().contiguous(), Wf.detach().contiguous(), bf.detach().contiguous()
+    S = torch.empty((B, m, Cout), dtype=torch.float32, device=p.device)
+    check(lib.nps_spectral1d_film_scale(ptr(p), ptr(Wf), ptr(bf), ptr(S), B, p.shape[1], Cout, m, int(mode),
+                                        stream_ptr()), "spectral1d_film_scale")
+    return S
+
+
+def spectral1d_mid(srcs: Sequence[Src], wpack: torch.Tensor, m: int, Cout: int, film=None):
+    """(X, Y, S): the retained spectrum of the sources, the mixed (and FiLM-scaled) modes, the FiLM factor."""
+    X = spectral1d_dft(srcs, m)
+    B, _, Cin = X.shape
+    S = film1d_scale(film, B, Cout, m) if film is not None else None
+    Y = torch.empty((B, m, Cout), dtype=torch.complex64, device=X.device)
+    spectral_mix(X, wpack, Y, B, 1, m, Cin, Cout, S)
+    return X, Y, S
+
+
+def spectral_conv1d(srcs: Sequence[Src], wpack: torch.Tensor, m: int, Cout: int, out: Optional[torch.Tensor] = None,
+                    accumulate=False, addend=None, act=0, film=None) -> torch.Tensor:
+    """y = irfft(P(rfft(x))) on the retained modes (proc_fno.py:199-222), channels-last (B, L, C) in / out (or the
+    (B, 1, L, C) view the 1x1 conv takes); film as in film1d_scale."""
+    L = srcs[0].t.shape[-2]
+    _, Y, _ = spectral1d_mid(srcs, wpack, m, Cout, film=film)
+    return spectral1d_idft(Y, L, out=out, accumulate=accumulate, addend=addend, act=act)
+
+
 def pack_spectral3d_weight(ws: Sequence[torch.Tensor], D: int, H: int) -> torch.Tensor:
     """SpectralConv3d weights1..4 (Cin, Cout, m1, m2, m3) complex64 -> wpack [R1][R2][m3][Cin][Cout]."""
     w1, w2, w3, w4 = [w.detach().contiguous() for w in ws]
