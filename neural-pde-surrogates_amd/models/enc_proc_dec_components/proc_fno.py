@@ -274,6 +274,15 @@ class FNO_Layer(nn.Module):
         return y.squeeze(2) if self.num_spatial_dims == 1 else y
 
 
+def _film(conv, p):
+    """ops' FiLM operand (p, weights_feat.weight, weights_feat.bias, transform_mode) of a SpectralConv1d / 2d; None
+    without feature_transform (p is then ignored, as in the reference)."""
+    if not conv.feature_transform:
+        return None
+    assert p is not None  # proc_fno.py:210, :272: we must have supplied params
+    return (p, conv.weights_feat.weight, conv.weights_feat.bias, conv.transform_mode)
+
+
 class SpectralConv2d(nn.Module):
     """proc_fno.py:225-288: rfft2 -> per-mode complex mixing of the 2 retained corners -> irfft2."""
 
@@ -303,27 +312,19 @@ class SpectralConv2d(nn.Module):
             self._pk_key = key
         return self._pk
 
-    def film(self, p):
-        """ops' FiLM operand (p, weights_feat.weight, weights_feat.bias, transform_mode); None without
-        feature_transform (p is then ignored, as in the reference)."""
-        if not self.feature_transform:
-            return None
-        assert p is not None  # proc_fno.py:272: we must have supplied params
-        return (p, self.weights_feat.weight, self.weights_feat.bias, self.transform_mode)
-
     def run(self, srcs, out=None, accumulate=False, addend=None, act=0, p=None):
         H = srcs[0].t.shape[1]
         return ops.spectral_conv2d(srcs, self.packed(H), self.modes1, self.modes2, self.out_channels, out=out,
-                                   accumulate=accumulate, addend=addend, act=act, film=self.film(p))
+                                   accumulate=accumulate, addend=addend, act=act, film=_film(self, p))
 
     def run_z(self, srcs, p=None):
         """The spectrum Z (B, H, m2, Cout) before the W-pass synthesis (ops.spectral_z): the FNO layer hands it to
         its 1x1 `w`, whose epilogue synthesises it (conv2d(spec=...))."""
         H = srcs[0].t.shape[1]
-        return ops.spectral_z(srcs, self.packed(H), self.modes1, self.modes2, self.out_channels, film=self.film(p))
+        return ops.spectral_z(srcs, self.packed(H), self.modes1, self.modes2, self.out_channels, film=_film(self, p))
 
     def forward(self, x, p=None):
-        film = self.film(p)
+        film = _film(self, p)
         # the module's own NCHW tensors go straight to the channels-first W passes: no layout round trip
         H, W = x.shape[2:4]
         if not (self.modes1 <= H and self.modes2 <= W // 2 + 1):
@@ -358,25 +359,17 @@ class SpectralConv1d(nn.Module):
             self._pk_key = key
         return self._pk
 
-    def film(self, p):
-        """ops' FiLM operand (p, weights_feat.weight, weights_feat.bias, transform_mode); None without
-        feature_transform (p is then ignored, as in the reference)."""
-        if not self.feature_transform:
-            return None
-        assert p is not None  # proc_fno.py:210: we must have supplied params
-        return (p, self.weights_feat.weight, self.weights_feat.bias, self.transform_mode)
-
     def run(self, srcs, out=None, accumulate=False, addend=None, act=0, p=None):
         """srcs: channels-last (B, L, C) sources, or their (B, 1, L, C) views.  Returns (B, L, Cout), or `out`."""
         return ops.spectral_conv1d(srcs, self.packed(), self.modes1, self.out_channels, out=out,
-                                   accumulate=accumulate, addend=addend, act=act, film=self.film(p))
+                                   accumulate=accumulate, addend=addend, act=act, film=_film(self, p))
 
     def run_ad(self, x, p=None):
         """Differentiable form on a channels-last (B, L, Cin) tensor (or its (B, 1, L, Cin) view)."""
         return ad.spectral_conv1d_film(self, x, p) if self.feature_transform else ad.spectral_conv1d(self, x)
 
     def forward(self, x, p=None):
-        film = self.film(p)
+        film = _film(self, p)
         L = x.shape[2]  # x (B, C, L), transposed on the (B, C, 1, L) view by the layout kernels
         ops.check_modes1d(L, self.modes1)
         if use_autograd(self):

@@ -578,92 +578,128 @@ def to_nchw(x):
 
 
 # ------------------------------------------------------------------------- spectral conv
+# One Function per dimension.  meta[0] is the activation layout, ops.NhwcW or ops.NchwW (ops.py, W-pass adapters): it
+# issues the W passes, and everything between them is written once, here and in ops.spectral2d_fwd / spectral3d_fwd.
+def _spec2d_bwd_mid(ctx, gZ):
+    """The layout-independent middle of the SpectralConv2d backward: gZ (the W pass's adjoint of gy) ->
+    (gX2, gwp, dp, dWf, dbf).  With FiLM the unscaled mixer output is formed again from the saved X2 (never Y / S)."""
+    _, m1, m2, Cout, mode = ctx.meta
+    B, H, W, Cin = ctx.shape
+    X2, wpack, *film = ctx.saved_tensors
+    R = X2.shape[1]
+    dev = gZ.device
+    s = stream_ptr()
+    c64 = torch.complex64
+    gY = torch.empty((B, R, m2, Cout), dtype=c64, device=dev)
+    gX2 = torch.empty((B, R, m2, Cin), dtype=c64, device=dev)
+    gwp = torch.empty((R, m2, Cin, Cout), dtype=c64, device=dev)
+    check(lib.nps_spectral_dft_h(ptr(gZ), ptr(gY), B, H, m1, m2, Cout, s), "spectral_dft_h (bwd)")
+    dp = dWf = dbf = None
+    if film:
+        S, p, Wf = film
+        Yu = torch.empty((B, R, m2, Cout), dtype=c64, device=dev)
+        gS = torch.empty((B, R, m2, Cout), dtype=torch.float32, device=dev)
+        check(lib.nps_spectral_mix(ptr(X2), ptr(wpack), ptr(Yu), B, R, m2, Cin, Cout, s), "spectral_mix (bwd)")
+        check(lib.nps_spectral_film_bwd(ptr(Yu), ptr(S), ptr(gY), ptr(gS), B, R, m2, Cout, s), "spectral_film_bwd")
+        need = ctx.needs_input_grad[5:8]
+        dp = torch.empty_like(p) if need[0] else None
+        dWf = torch.empty_like(Wf) if need[1] else None
+        dbf = torch.empty((Wf.shape[0],), dtype=torch.float32, device=dev) if need[2] else None
+        if any(need):
+            check(lib.nps_spectral_film_param_bwd(ptr(gS), ptr(p), ptr(Wf), ptr(dWf), ptr(dbf), ptr(dp), B, p.shape[1],
+                                                  Cout, H, m1, m2, mode, s), "spectral_film_param_bwd")
+    check(lib.nps_spectral_mix_bwd(ptr(X2), ptr(wpack), ptr(gY), ptr(gX2), ptr(gwp), B, R, m2, Cin, Cout, s),
+          "spectral_mix_bwd")
+    return gX2, gwp, dp, dWf, dbf
+
+
 class SpectralConv2dFn(torch.autograd.Function):
-    """SpectralConv2d.forward (proc_fno.py:257-288) and its torch.fft / complex-einsum backward."""
+    """SpectralConv2d.forward (proc_fno.py:257-288) and its torch.fft / complex-einsum backward, on NHWC x
+    (B, H, W, Cin) or, with no transposes, on the module's own NCHW x (B, Cin, H, W) (meta's layout).  With FiLM
+    conditioning (:271-284; p, Wf, bf given, else None) the mixed modes are multiplied by the real factor S
+    (ops.film_scale) of p (B, K) and weights_feat, which then get gradients too.  Saved: (X2, wpack[, S, p, Wf])."""
 
     @staticmethod
-    def forward(ctx, meta, x, w1, w2, wpack):
-        m1, m2, Cout = meta
-        x = _c(x)
-        B, H, W, Cin = x.shape
-        R = min(H, 2 * m1)
-        dev = x.device
-        X1 = torch.empty((B, H, m2, Cin), dtype=torch.complex64, device=dev)
-        X2 = torch.empty((B, R, m2, Cin), dtype=torch.complex64, device=dev)
-        Y = torch.empty((B, R, m2, Cout), dtype=torch.complex64, device=dev)
-        Z = torch.empty((B, H, m2, Cout), dtype=torch.complex64, device=dev)
-        y = ops.empty_nhwc(B, H, W, Cout, x)
-        s = stream_ptr()
-        check(lib.nps_spectral_dft_w(ops._c_src([Src(x)]), 1, B, H, W, Cin, m2, ptr(X1), s), "spectral_dft_w")
-        check(lib.nps_spectral_dft_h(ptr(X1), ptr(X2), B, H, m1, m2, Cin, s), "spectral_dft_h")
-        check(lib.nps_spectral_mix(ptr(X2), ptr(wpack), ptr(Y), B, R, m2, Cin, Cout, s), "spectral_mix")
-        check(lib.nps_spectral_idft_h(ptr(Y), ptr(Z), B, H, m1, m2, Cout, s), "spectral_idft_h")
-        check(lib.nps_spectral_idft_w(ptr(Z), ptr(y), B, H, W, m2, Cout, 0, None, 0, ops.new_tag(y), s),
-              "spectral_idft_w")
-        ctx.meta, ctx.shape = meta, (B, H, W, Cin)
-        ctx.save_for_backward(X2, wpack)
+    def forward(ctx, meta, x, w1, w2, wpack, p, Wf, bf):
+        Lay, m1, m2, Cout, mode = meta
+        lay = Lay.of(x)
+        film = None if p is None else (_c(p), _c(Wf), _c(bf), mode)
+        X2, Z, S = ops.spectral2d_fwd(lay, wpack, m1, m2, Cout, film=film)
+        y = lay.new_out(Cout)
+        lay.idft_w(Z, y, m2, Cout)
+        ctx.meta, ctx.shape = meta, lay.dims
+        ctx.save_for_backward(X2, wpack, *(() if film is None else (S, film[0], film[1])))
         return y
 
     @staticmethod
     def backward(ctx, gy):
-        m1, m2, Cout = ctx.meta
+        Lay, m1, m2, Cout, _ = ctx.meta
         B, H, W, Cin = ctx.shape
-        X2, wpack = ctx.saved_tensors
-        R = X2.shape[1]
-        gy = _c(gy)
         dev = gy.device
         s = stream_ptr()
         gZ = torch.empty((B, H, m2, Cout), dtype=torch.complex64, device=dev)
-        gY = torch.empty((B, R, m2, Cout), dtype=torch.complex64, device=dev)
-        gX2 = torch.empty((B, R, m2, Cin), dtype=torch.complex64, device=dev)
-        gwp = torch.empty((R, m2, Cin, Cout), dtype=torch.complex64, device=dev)
-        check(lib.nps_spectral_idft_w_bwd(ptr(gy), ptr(gZ), B, H, W, m2, Cout, s), "spectral_idft_w_bwd")
-        check(lib.nps_spectral_dft_h(ptr(gZ), ptr(gY), B, H, m1, m2, Cout, s), "spectral_dft_h (bwd)")
-        check(lib.nps_spectral_mix_bwd(ptr(X2), ptr(wpack), ptr(gY), ptr(gX2), ptr(gwp), B, R, m2, Cin, Cout, s),
-              "spectral_mix_bwd")
+        Lay.idft_w_bwd(gy, gZ, B, H, W, m2, Cout)
+        gX2, gwp, dp, dWf, dbf = _spec2d_bwd_mid(ctx, gZ)
         dx = dw1 = dw2 = None
         if ctx.needs_input_grad[1]:
             gX1 = torch.empty((B, H, m2, Cin), dtype=torch.complex64, device=dev)
             check(lib.nps_spectral_idft_h(ptr(gX2), ptr(gX1), B, H, m1, m2, Cin, s), "spectral_idft_h (bwd)")
-            dx = torch.empty((B, H, W, Cin), dtype=torch.float32, device=dev)
-            check(lib.nps_spectral_dft_w_bwd(ptr(gX1), ptr(dx), B, H, W, m2, Cin, s), "spectral_dft_w_bwd")
+            dx = Lay.dft_w_bwd(gX1, B, H, W, m2, Cin)
         if ctx.needs_input_grad[2] or ctx.needs_input_grad[3]:
             dw1 = torch.empty((Cin, Cout, m1, m2), dtype=torch.complex64, device=dev)
             dw2 = torch.empty((Cin, Cout, m1, m2), dtype=torch.complex64, device=dev)
             check(lib.nps_spectral_unpack_grad(ptr(gwp), ptr(dw1), ptr(dw2), Cin, Cout, H, m1, m2, s),
                   "spectral_unpack_grad")
-        return None, dx, dw1, dw2, None
+        return None, dx, dw1, dw2, None, dp, dWf, dbf
+
+
+def _spectral_conv2d(Lay, module, x, H, p=None):
+    mode, Wf, bf = (None, None, None) if p is None else (int(module.transform_mode), module.weights_feat.weight,
+                                                         module.weights_feat.bias)
+    return SpectralConv2dFn.apply((Lay, module.modes1, module.modes2, module.out_channels, mode), x, module.weights1,
+                                  module.weights2, module.packed(H), p, Wf, bf)
 
 
 def spectral_conv2d(module, x):
-    H = x.shape[1]
-    return SpectralConv2dFn.apply((module.modes1, module.modes2, module.out_channels), x, module.weights1,
-                                  module.weights2, module.packed(H))
+    return _spectral_conv2d(ops.NhwcW, module, x, x.shape[1])
+
+
+def spectral_conv2d_nchw(module, x):
+    return _spectral_conv2d(ops.NchwW, module, x, x.shape[2])
+
+
+def spectral_conv2d_film(module, x, p):
+    assert p is not None  # proc_fno.py:272: we must have supplied params
+    return _spectral_conv2d(ops.NhwcW, module, x, x.shape[1], p)
+
+
+def spectral_conv2d_film_nchw(module, x, p):
+    assert p is not None  # proc_fno.py:272: we must have supplied params
+    return _spectral_conv2d(ops.NchwW, module, x, x.shape[2], p)
 
 
 class SpectralConv3dFn(torch.autograd.Function):
-    """SpectralConv3d.forward (proc_fno.py:334-376) and its torch.fft / complex-einsum backward, axis by
-    axis with the 2-D kernels (include/nps.h, SpectralConv3d)."""
+    """SpectralConv3d.forward (proc_fno.py:334-376) and its torch.fft / complex-einsum backward, axis by axis with
+    the 2-D kernels (include/nps.h, SpectralConv3d), on the NDHWC view x (B, D*H, W, Cin) or, with no transposes, on
+    the module's own NCDHW x (B, Cin, D, H, W) (meta's layout).  Saved: (X3, wpack)."""
 
     @staticmethod
     def forward(ctx, meta, x, w1, w2, w3, w4, wpack):
-        m1, m2, m3, Cout, D = meta
-        x = _c(x)  # (B, D*H, W, Cin)
-        B, DH, W, Cin = x.shape
-        H = DH // D
-        y = ops.empty_nhwc(B, DH, W, Cout, x)
-        X3 = ops.spectral_conv3d_stages([Src(x)], D, H, W, Cin, wpack, m1, m2, m3, Cout, y)
-        ctx.meta, ctx.shape = meta, (B, D, H, W, Cin)
+        Lay, m1, m2, m3, Cout, D = meta
+        lay = Lay.of(x)
+        B, DH, W, Cin = lay.dims
+        y = lay.new_out(Cout)
+        X3 = ops.spectral3d_fwd(lay, D, wpack, m1, m2, m3, Cout, y)
+        ctx.meta, ctx.shape, ctx.xshape = meta, (B, D, DH // D, W, Cin), tuple(x.shape)
         ctx.save_for_backward(X3, wpack)
         return y
 
     @staticmethod
     def backward(ctx, gy):
-        m1, m2, m3, Cout, D = ctx.meta
+        Lay, m1, m2, m3, Cout, _ = ctx.meta
         B, D, H, W, Cin = ctx.shape
         X3, wpack = ctx.saved_tensors
         R1, R2 = min(D, 2 * m1), min(H, 2 * m2)
-        gy = _c(gy)
         dev = gy.device
         c64 = torch.complex64
         s = stream_ptr()
@@ -672,7 +708,7 @@ class SpectralConv3dFn(torch.autograd.Function):
         gY = torch.empty((B, R1, R2 * m3, Cout), dtype=c64, device=dev)
         gX3 = torch.empty((B, R1, R2 * m3, Cin), dtype=c64, device=dev)
         gwp = torch.empty((R1, R2, m3, Cin, Cout), dtype=c64, device=dev)
-        check(lib.nps_spectral_idft_w_bwd(ptr(gy), ptr(gZ2), B, D * H, W, m3, Cout, s), "spectral3d idft_w_bwd")
+        Lay.idft_w_bwd(gy, gZ2, B, D * H, W, m3, Cout)
         check(lib.nps_spectral_dft_h(ptr(gZ2), ptr(gZ1), B * D, H, m2, m3, Cout, s), "spectral3d dft_h (H, bwd)")
         check(lib.nps_spectral_dft_h(ptr(gZ1), ptr(gY), B, D, m1, R2 * m3, Cout, s), "spectral3d dft_h (D, bwd)")
         check(lib.nps_spectral_mix_bwd(ptr(X3), ptr(wpack), ptr(gY), ptr(gX3), ptr(gwp), B, R1, R2 * m3, Cin, Cout,
@@ -684,8 +720,7 @@ class SpectralConv3dFn(torch.autograd.Function):
             gX1 = torch.empty((B * D, H, m3, Cin), dtype=c64, device=dev)
             check(lib.nps_spectral_idft_h(ptr(gX3), ptr(gX2), B, D, m1, R2 * m3, Cin, s), "spectral3d idft_h (D, bwd)")
             check(lib.nps_spectral_idft_h(ptr(gX2), ptr(gX1), B * D, H, m2, m3, Cin, s), "spectral3d idft_h (H, bwd)")
-            dx = torch.empty((B, D * H, W, Cin), dtype=torch.float32, device=dev)
-            check(lib.nps_spectral_dft_w_bwd(ptr(gX1), ptr(dx), B, D * H, W, m3, Cin, s), "spectral3d dft_w_bwd")
+            dx = Lay.dft_w_bwd(gX1, B, D * H, W, m3, Cin).view(ctx.xshape)
         if any(ctx.needs_input_grad[2:6]):
             gws = [torch.empty((Cin, Cout, m1, m2, m3), dtype=c64, device=dev) for _ in range(4)]
             check(lib.nps_spectral3d_unpack_grad(ptr(gwp), *[ptr(g) for g in gws], Cin, Cout, D, H, m1, m2, m3, s),
@@ -693,360 +728,89 @@ class SpectralConv3dFn(torch.autograd.Function):
         return (None, dx, *gws, None)
 
 
-def spectral_conv3d(module, x, D):
-    """x: (B, D*H, W, Cin) NDHWC view -> (B, D*H, W, Cout)."""
-    H = x.shape[1] // D
-    return SpectralConv3dFn.apply((module.modes1, module.modes2, module.modes3, module.out_channels, D), x,
+def _spectral_conv3d(Lay, module, x, D, H):
+    return SpectralConv3dFn.apply((Lay, module.modes1, module.modes2, module.modes3, module.out_channels, D), x,
                                   module.weights1, module.weights2, module.weights3, module.weights4,
                                   module.packed(D, H))
 
 
-class SpectralConv2dNchwFn(torch.autograd.Function):
-    """SpectralConv2dFn on the module's own NCHW tensors: x (B, Cin, H, W) -> (B, Cout, H, W), gy read and dx
-    written channels-first (no transposes); the saved tensors are the same X2 and wpack."""
-
-    @staticmethod
-    def forward(ctx, meta, x, w1, w2, wpack):
-        m1, m2, Cout = meta
-        x, x_bs = ops.channels_first(x)
-        B, Cin, H, W = x.shape
-        y = torch.empty((B, Cout, H, W), dtype=torch.float32, device=x.device)
-        X2 = ops.spectral_conv2d_nchw_stages(x, x_bs, wpack, m1, m2, Cout, y, 0)
-        ctx.meta, ctx.shape = meta, (B, H, W, Cin)
-        ctx.save_for_backward(X2, wpack)
-        return y
-
-    @staticmethod
-    def backward(ctx, gy):
-        m1, m2, Cout = ctx.meta
-        B, H, W, Cin = ctx.shape
-        X2, wpack = ctx.saved_tensors
-        R = X2.shape[1]
-        gy, gy_bs = ops.channels_first(gy)
-        dev = gy.device
-        s = stream_ptr()
-        gZ = torch.empty((B, H, m2, Cout), dtype=torch.complex64, device=dev)
-        gY = torch.empty((B, R, m2, Cout), dtype=torch.complex64, device=dev)
-        gX2 = torch.empty((B, R, m2, Cin), dtype=torch.complex64, device=dev)
-        gwp = torch.empty((R, m2, Cin, Cout), dtype=torch.complex64, device=dev)
-        check(lib.nps_spectral_idft_w_bwd_nchw(ptr(gy), gy_bs, ptr(gZ), B, H, W, m2, Cout, s),
-              "spectral_idft_w_bwd_nchw")
-        check(lib.nps_spectral_dft_h(ptr(gZ), ptr(gY), B, H, m1, m2, Cout, s), "spectral_dft_h (bwd)")
-        check(lib.nps_spectral_mix_bwd(ptr(X2), ptr(wpack), ptr(gY), ptr(gX2), ptr(gwp), B, R, m2, Cin, Cout, s),
-              "spectral_mix_bwd")
-        dx = dw1 = dw2 = None
-        if ctx.needs_input_grad[1]:
-            gX1 = torch.empty((B, H, m2, Cin), dtype=torch.complex64, device=dev)
-            check(lib.nps_spectral_idft_h(ptr(gX2), ptr(gX1), B, H, m1, m2, Cin, s), "spectral_idft_h (bwd)")
-            dx = torch.empty((B, Cin, H, W), dtype=torch.float32, device=dev)
-            check(lib.nps_spectral_dft_w_bwd_nchw(ptr(gX1), ptr(dx), 0, B, H, W, m2, Cin, s),
-                  "spectral_dft_w_bwd_nchw")
-        if ctx.needs_input_grad[2] or ctx.needs_input_grad[3]:
-            dw1 = torch.empty((Cin, Cout, m1, m2), dtype=torch.complex64, device=dev)
-            dw2 = torch.empty((Cin, Cout, m1, m2), dtype=torch.complex64, device=dev)
-            check(lib.nps_spectral_unpack_grad(ptr(gwp), ptr(dw1), ptr(dw2), Cin, Cout, H, m1, m2, s),
-                  "spectral_unpack_grad")
-        return None, dx, dw1, dw2, None
+def spectral_conv3d(module, x, D):
+    """x: (B, D*H, W, Cin) NDHWC view -> (B, D*H, W, Cout)."""
+    return _spectral_conv3d(ops.NhwcW, module, x, D, x.shape[1] // D)
 
 
-def spectral_conv2d_nchw(module, x):
-    H = x.shape[2]
-    return SpectralConv2dNchwFn.apply((module.modes1, module.modes2, module.out_channels), x, module.weights1,
-                                      module.weights2, module.packed(H))
-
-
-def _film_bwd_mid(ctx, gZ):
-    """The layout-independent middle of the FiLM SpectralConv2d backward: gZ (the W pass's adjoint of gy) ->
-    (gX2, gwp, dp, dWf, dbf).  The unscaled mixer output is formed again from the saved X2 (never Y / S)."""
-    m1, m2, Cout, mode = ctx.meta
-    B, H, W, Cin = ctx.shape
-    X2, wpack, S, p, Wf = ctx.saved_tensors
-    R, K = X2.shape[1], p.shape[1]
-    dev = gZ.device
-    s = stream_ptr()
-    c64 = torch.complex64
-    gY = torch.empty((B, R, m2, Cout), dtype=c64, device=dev)
-    Yu = torch.empty((B, R, m2, Cout), dtype=c64, device=dev)
-    gS = torch.empty((B, R, m2, Cout), dtype=torch.float32, device=dev)
-    gX2 = torch.empty((B, R, m2, Cin), dtype=c64, device=dev)
-    gwp = torch.empty((R, m2, Cin, Cout), dtype=c64, device=dev)
-    check(lib.nps_spectral_dft_h(ptr(gZ), ptr(gY), B, H, m1, m2, Cout, s), "spectral_dft_h (bwd)")
-    check(lib.nps_spectral_mix(ptr(X2), ptr(wpack), ptr(Yu), B, R, m2, Cin, Cout, s), "spectral_mix (bwd)")
-    check(lib.nps_spectral_film_bwd(ptr(Yu), ptr(S), ptr(gY), ptr(gS), B, R, m2, Cout, s), "spectral_film_bwd")
-    need = ctx.needs_input_grad[5:8]
-    dp = torch.empty_like(p) if need[0] else None
-    dWf = torch.empty_like(Wf) if need[1] else None
-    dbf = torch.empty((Wf.shape[0],), dtype=torch.float32, device=dev) if need[2] else None
-    if any(need):
-        check(lib.nps_spectral_film_param_bwd(ptr(gS), ptr(p), ptr(Wf), ptr(dWf), ptr(dbf), ptr(dp), B, K, Cout, H,
-                                              m1, m2, mode, s), "spectral_film_param_bwd")
-    check(lib.nps_spectral_mix_bwd(ptr(X2), ptr(wpack), ptr(gY), ptr(gX2), ptr(gwp), B, R, m2, Cin, Cout, s),
-          "spectral_mix_bwd")
-    return gX2, gwp, dp, dWf, dbf
-
-
-def _film_unpack(ctx, gwp, dev):
-    m1, m2, Cout, _ = ctx.meta
-    B, H, W, Cin = ctx.shape
-    dw1 = torch.empty((Cin, Cout, m1, m2), dtype=torch.complex64, device=dev)
-    dw2 = torch.empty((Cin, Cout, m1, m2), dtype=torch.complex64, device=dev)
-    check(lib.nps_spectral_unpack_grad(ptr(gwp), ptr(dw1), ptr(dw2), Cin, Cout, H, m1, m2, stream_ptr()),
-          "spectral_unpack_grad")
-    return dw1, dw2
-
-
-class SpectralConv2dFilmFn(torch.autograd.Function):
-    """SpectralConv2d.forward with FiLM conditioning (proc_fno.py:257-288 with :271-284), NHWC: the mixed modes
-    times the real factor S (ops.film_scale) of p (B, K) and weights_feat; gradients for x, weights1/2, p and
-    weights_feat's weight and bias."""
-
-    @staticmethod
-    def forward(ctx, meta, x, w1, w2, wpack, p, Wf, bf):
-        m1, m2, Cout, mode = meta
-        x = _c(x)
-        B, H, W, Cin = x.shape
-        p, Wf, bf = _c(p), _c(Wf), _c(bf)
-        dev = x.device
-        X1 = torch.empty((B, H, m2, Cin), dtype=torch.complex64, device=dev)
-        y = ops.empty_nhwc(B, H, W, Cout, x)
-        s = stream_ptr()
-        check(lib.nps_spectral_dft_w(ops._c_src([Src(x)]), 1, B, H, W, Cin, m2, ptr(X1), s), "spectral_dft_w")
-        X2, Z, S = ops.spectral_mid2d(X1, wpack, B, H, m1, m2, Cin, Cout, film=(p, Wf, bf, mode))
-        check(lib.nps_spectral_idft_w(ptr(Z), ptr(y), B, H, W, m2, Cout, 0, None, 0, ops.new_tag(y), s),
-              "spectral_idft_w")
-        ctx.meta, ctx.shape = meta, (B, H, W, Cin)
-        ctx.save_for_backward(X2, wpack, S, p, Wf)
-        return y
-
-    @staticmethod
-    def backward(ctx, gy):
-        m1, m2, Cout, _ = ctx.meta
-        B, H, W, Cin = ctx.shape
-        gy = _c(gy)
-        dev = gy.device
-        s = stream_ptr()
-        gZ = torch.empty((B, H, m2, Cout), dtype=torch.complex64, device=dev)
-        check(lib.nps_spectral_idft_w_bwd(ptr(gy), ptr(gZ), B, H, W, m2, Cout, s), "spectral_idft_w_bwd")
-        gX2, gwp, dp, dWf, dbf = _film_bwd_mid(ctx, gZ)
-        dx = dw1 = dw2 = None
-        if ctx.needs_input_grad[1]:
-            gX1 = torch.empty((B, H, m2, Cin), dtype=torch.complex64, device=dev)
-            check(lib.nps_spectral_idft_h(ptr(gX2), ptr(gX1), B, H, m1, m2, Cin, s), "spectral_idft_h (bwd)")
-            dx = torch.empty((B, H, W, Cin), dtype=torch.float32, device=dev)
-            check(lib.nps_spectral_dft_w_bwd(ptr(gX1), ptr(dx), B, H, W, m2, Cin, s), "spectral_dft_w_bwd")
-        if ctx.needs_input_grad[2] or ctx.needs_input_grad[3]:
-            dw1, dw2 = _film_unpack(ctx, gwp, dev)
-        return None, dx, dw1, dw2, None, dp, dWf, dbf
-
-
-class SpectralConv2dFilmNchwFn(torch.autograd.Function):
-    """SpectralConv2dFilmFn on the module's own NCHW tensors (as SpectralConv2dNchwFn: no transposes)."""
-
-    @staticmethod
-    def forward(ctx, meta, x, w1, w2, wpack, p, Wf, bf):
-        m1, m2, Cout, mode = meta
-        x, x_bs = ops.channels_first(x)
-        B, Cin, H, W = x.shape
-        p, Wf, bf = _c(p), _c(Wf), _c(bf)
-        y = torch.empty((B, Cout, H, W), dtype=torch.float32, device=x.device)
-        X2, S = ops.spectral_conv2d_nchw_stages(x, x_bs, wpack, m1, m2, Cout, y, 0, film=(p, Wf, bf, mode))
-        ctx.meta, ctx.shape = meta, (B, H, W, Cin)
-        ctx.save_for_backward(X2, wpack, S, p, Wf)
-        return y
-
-    @staticmethod
-    def backward(ctx, gy):
-        m1, m2, Cout, _ = ctx.meta
-        B, H, W, Cin = ctx.shape
-        gy, gy_bs = ops.channels_first(gy)
-        dev = gy.device
-        s = stream_ptr()
-        gZ = torch.empty((B, H, m2, Cout), dtype=torch.complex64, device=dev)
-        check(lib.nps_spectral_idft_w_bwd_nchw(ptr(gy), gy_bs, ptr(gZ), B, H, W, m2, Cout, s),
-              "spectral_idft_w_bwd_nchw")
-        gX2, gwp, dp, dWf, dbf = _film_bwd_mid(ctx, gZ)
-        dx = dw1 = dw2 = None
-        if ctx.needs_input_grad[1]:
-            gX1 = torch.empty((B, H, m2, Cin), dtype=torch.complex64, device=dev)
-            check(lib.nps_spectral_idft_h(ptr(gX2), ptr(gX1), B, H, m1, m2, Cin, s), "spectral_idft_h (bwd)")
-            dx = torch.empty((B, Cin, H, W), dtype=torch.float32, device=dev)
-            check(lib.nps_spectral_dft_w_bwd_nchw(ptr(gX1), ptr(dx), 0, B, H, W, m2, Cin, s),
-                  "spectral_dft_w_bwd_nchw")
-        if ctx.needs_input_grad[2] or ctx.needs_input_grad[3]:
-            dw1, dw2 = _film_unpack(ctx, gwp, dev)
-        return None, dx, dw1, dw2, None, dp, dWf, dbf
-
-
-def _film_args(module, p, H):
-    assert p is not None  # proc_fno.py:272: we must have supplied params
-    return ((module.modes1, module.modes2, module.out_channels, int(module.transform_mode)), module.weights1,
-            module.weights2, module.packed(H), p, module.weights_feat.weight, module.weights_feat.bias)
-
-
-def spectral_conv2d_film(module, x, p):
-    meta, *rest = _film_args(module, p, x.shape[1])
-    return SpectralConv2dFilmFn.apply(meta, x, *rest)
-
-
-def spectral_conv2d_film_nchw(module, x, p):
-    meta, *rest = _film_args(module, p, x.shape[2])
-    return SpectralConv2dFilmNchwFn.apply(meta, x, *rest)
+def spectral_conv3d_nchw(module, x):
+    """x: (B, Cin, D, H, W) -> (B, Cout, D, H, W)."""
+    return _spectral_conv3d(ops.NchwW, module, x, x.shape[2], x.shape[3])
 
 
 # ------------------------------------------------------------------------- spectral conv, 1-D
-def _spec1d_bwd(ctx, gy, film):
-    """The SpectralConv1d backward (SURVEY.md §0.8 in one dimension): gy -> (dx, dw, dp, dWf, dbf)."""
-    m, Cout = ctx.meta[:2]
-    B, L, Cin = ctx.shape
-    X, wpack = ctx.saved_tensors[:2]
-    gy = _c(gy)
-    dev = gy.device
-    s = stream_ptr()
-    c64 = torch.complex64
-    gY = ops.spectral1d_dft([Src(gy.reshape(B, L, Cout))], m, adjoint=True)  # irfft's adjoint: c_k / L
-    dp = dWf = dbf = None
-    if film:
-        mode = ctx.meta[2]
-        S, p, Wf = ctx.saved_tensors[2:5]
-        K = p.shape[1]
-        # the unscaled mixer output again from the saved X (never Y / S: S may be zero)
-        Yu = torch.empty((B, m, Cout), dtype=c64, device=dev)
-        gS = torch.empty((B, m, Cout), dtype=torch.float32, device=dev)
-        check(lib.nps_spectral_mix(ptr(X), ptr(wpack), ptr(Yu), B, 1, m, Cin, Cout, s), "spectral_mix (bwd)")
-        check(lib.nps_spectral_film_bwd(ptr(Yu), ptr(S), ptr(gY), ptr(gS), B, 1, m, Cout, s), "spectral_film_bwd")
-        need = ctx.needs_input_grad[4:7]
-        dp = torch.empty_like(p) if need[0] else None
-        dWf = torch.empty_like(Wf) if need[1] else None
-        dbf = torch.empty((Wf.shape[0],), dtype=torch.float32, device=dev) if need[2] else None
-        if any(need):
-            check(lib.nps_spectral1d_film_param_bwd(ptr(gS), ptr(p), ptr(Wf), ptr(dWf), ptr(dbf), ptr(dp), B, K, Cout,
-                                                    m, mode, s), "spectral1d_film_param_bwd")
-    gX = torch.empty((B, m, Cin), dtype=c64, device=dev)
-    gwp = torch.empty((lib.nps_spectral1d_mix_bwd_parts(B), m, Cin, Cout), dtype=c64, device=dev)  # result: part 0
-    check(lib.nps_spectral1d_mix_bwd(ptr(X), ptr(wpack), ptr(gY), ptr(gX), ptr(gwp), B, m, Cin, Cout, s),
-          "spectral1d_mix_bwd")
-    dx = dw = None
-    if ctx.needs_input_grad[1]:
-        dx = ops.spectral1d_idft(gX, L, adjoint=True).reshape(ctx.xshape)
-    if ctx.needs_input_grad[2]:
-        dw = torch.empty((Cin, Cout, m), dtype=c64, device=dev)
-        check(lib.nps_spectral1d_unpack_grad(ptr(gwp), ptr(dw), Cin, Cout, m, s), "spectral1d_unpack_grad")
-    return dx, dw, dp, dWf, dbf
-
-
 class SpectralConv1dFn(torch.autograd.Function):
     """SpectralConv1d.forward (proc_fno.py:199-222) on channels-last x (B, L, Cin) (or its (B, 1, L, Cin) view) and
-    its torch.fft / complex-einsum backward."""
-
-    @staticmethod
-    def forward(ctx, meta, x, w, wpack):
-        m, Cout = meta
-        x = _c(x)
-        B, L, Cin = x.shape[0], x.shape[-2], x.shape[-1]
-        X, Y, _ = ops.spectral1d_mid([Src(x)], wpack, m, Cout)
-        y = ops.spectral1d_idft(Y, L).reshape(x.shape[:-1] + (Cout,))
-        ctx.meta, ctx.shape, ctx.xshape = meta, (B, L, Cin), tuple(x.shape)
-        ctx.save_for_backward(X, wpack)
-        return y
-
-    @staticmethod
-    def backward(ctx, gy):
-        dx, dw, _, _, _ = _spec1d_bwd(ctx, gy, False)
-        return None, dx, dw, None
-
-
-class SpectralConv1dFilmFn(torch.autograd.Function):
-    """SpectralConv1dFn with FiLM conditioning (proc_fno.py:209-218): the mixed modes times the real factor S
-    (ops.film1d_scale); gradients for x, weights1, p and weights_feat's weight and bias."""
+    its torch.fft / complex-einsum backward (SURVEY.md §0.8 in one dimension).  With FiLM conditioning (:209-218; p,
+    Wf, bf given, else None) the mixed modes are multiplied by the real factor S (ops.film1d_scale), and p and
+    weights_feat's weight and bias get gradients too.  Saved: (X, wpack[, S, p, Wf])."""
 
     @staticmethod
     def forward(ctx, meta, x, w, wpack, p, Wf, bf):
         m, Cout, mode = meta
         x = _c(x)
         B, L, Cin = x.shape[0], x.shape[-2], x.shape[-1]
-        p, Wf, bf = _c(p), _c(Wf), _c(bf)
-        X, Y, S = ops.spectral1d_mid([Src(x)], wpack, m, Cout, film=(p, Wf, bf, mode))
+        film = None if p is None else (_c(p), _c(Wf), _c(bf), mode)
+        X, Y, S = ops.spectral1d_mid([Src(x)], wpack, m, Cout, film=film)
         y = ops.spectral1d_idft(Y, L).reshape(x.shape[:-1] + (Cout,))
         ctx.meta, ctx.shape, ctx.xshape = meta, (B, L, Cin), tuple(x.shape)
-        ctx.save_for_backward(X, wpack, S, p, Wf)
+        ctx.save_for_backward(X, wpack, *(() if film is None else (S, film[0], film[1])))
         return y
 
     @staticmethod
     def backward(ctx, gy):
-        dx, dw, dp, dWf, dbf = _spec1d_bwd(ctx, gy, True)
+        m, Cout, mode = ctx.meta
+        B, L, Cin = ctx.shape
+        X, wpack, *film = ctx.saved_tensors
+        gy = _c(gy)
+        dev = gy.device
+        s = stream_ptr()
+        c64 = torch.complex64
+        gY = ops.spectral1d_dft([Src(gy.reshape(B, L, Cout))], m, adjoint=True)  # irfft's adjoint: c_k / L
+        dp = dWf = dbf = None
+        if film:
+            S, p, Wf = film
+            # the unscaled mixer output again from the saved X (never Y / S: S may be zero)
+            Yu = torch.empty((B, m, Cout), dtype=c64, device=dev)
+            gS = torch.empty((B, m, Cout), dtype=torch.float32, device=dev)
+            check(lib.nps_spectral_mix(ptr(X), ptr(wpack), ptr(Yu), B, 1, m, Cin, Cout, s), "spectral_mix (bwd)")
+            check(lib.nps_spectral_film_bwd(ptr(Yu), ptr(S), ptr(gY), ptr(gS), B, 1, m, Cout, s), "spectral_film_bwd")
+            need = ctx.needs_input_grad[4:7]
+            dp = torch.empty_like(p) if need[0] else None
+            dWf = torch.empty_like(Wf) if need[1] else None
+            dbf = torch.empty((Wf.shape[0],), dtype=torch.float32, device=dev) if need[2] else None
+            if any(need):
+                check(lib.nps_spectral1d_film_param_bwd(ptr(gS), ptr(p), ptr(Wf), ptr(dWf), ptr(dbf), ptr(dp), B,
+                                                        p.shape[1], Cout, m, mode, s), "spectral1d_film_param_bwd")
+        gX = torch.empty((B, m, Cin), dtype=c64, device=dev)
+        gwp = torch.empty((lib.nps_spectral1d_mix_bwd_parts(B), m, Cin, Cout), dtype=c64, device=dev)  # result: part 0
+        check(lib.nps_spectral1d_mix_bwd(ptr(X), ptr(wpack), ptr(gY), ptr(gX), ptr(gwp), B, m, Cin, Cout, s),
+              "spectral1d_mix_bwd")
+        dx = dw = None
+        if ctx.needs_input_grad[1]:
+            dx = ops.spectral1d_idft(gX, L, adjoint=True).reshape(ctx.xshape)
+        if ctx.needs_input_grad[2]:
+            dw = torch.empty((Cin, Cout, m), dtype=c64, device=dev)
+            check(lib.nps_spectral1d_unpack_grad(ptr(gwp), ptr(dw), Cin, Cout, m, s), "spectral1d_unpack_grad")
         return None, dx, dw, None, dp, dWf, dbf
 
 
 def spectral_conv1d(module, x):
-    return SpectralConv1dFn.apply((module.modes1, module.out_channels), x, module.weights1, module.packed())
+    return SpectralConv1dFn.apply((module.modes1, module.out_channels, None), x, module.weights1, module.packed(),
+                                  None, None, None)
 
 
 def spectral_conv1d_film(module, x, p):
     assert p is not None  # proc_fno.py:210: we must have supplied params
-    return SpectralConv1dFilmFn.apply((module.modes1, module.out_channels, int(module.transform_mode)), x,
-                                      module.weights1, module.packed(), p, module.weights_feat.weight,
-                                      module.weights_feat.bias)
-
-
-class SpectralConv3dNchwFn(torch.autograd.Function):
-    """SpectralConv3dFn on the module's own NCDHW tensors: x (B, Cin, D, H, W) -> (B, Cout, D, H, W), gy read and
-    dx written channels-first; the saved tensors are the same X3 and wpack."""
-
-    @staticmethod
-    def forward(ctx, meta, x, w1, w2, w3, w4, wpack):
-        m1, m2, m3, Cout = meta
-        x, x_bs = ops.channels_first(x)
-        B, Cin, D, H, W = x.shape
-        y = torch.empty((B, Cout, D, H, W), dtype=torch.float32, device=x.device)
-        X3 = ops.spectral_conv3d_nchw_stages(x, x_bs, wpack, m1, m2, m3, Cout, y, 0)
-        ctx.meta, ctx.shape = meta, (B, D, H, W, Cin)
-        ctx.save_for_backward(X3, wpack)
-        return y
-
-    @staticmethod
-    def backward(ctx, gy):
-        m1, m2, m3, Cout = ctx.meta
-        B, D, H, W, Cin = ctx.shape
-        X3, wpack = ctx.saved_tensors
-        R1, R2 = min(D, 2 * m1), min(H, 2 * m2)
-        gy, gy_bs = ops.channels_first(gy)
-        dev = gy.device
-        c64 = torch.complex64
-        s = stream_ptr()
-        gZ2 = torch.empty((B, D * H, m3, Cout), dtype=c64, device=dev)
-        gZ1 = torch.empty((B * D, R2, m3, Cout), dtype=c64, device=dev)
-        gY = torch.empty((B, R1, R2 * m3, Cout), dtype=c64, device=dev)
-        gX3 = torch.empty((B, R1, R2 * m3, Cin), dtype=c64, device=dev)
-        gwp = torch.empty((R1, R2, m3, Cin, Cout), dtype=c64, device=dev)
-        check(lib.nps_spectral_idft_w_bwd_nchw(ptr(gy), gy_bs, ptr(gZ2), B, D * H, W, m3, Cout, s),
-              "spectral3d idft_w_bwd_nchw")
-        check(lib.nps_spectral_dft_h(ptr(gZ2), ptr(gZ1), B * D, H, m2, m3, Cout, s), "spectral3d dft_h (H, bwd)")
-        check(lib.nps_spectral_dft_h(ptr(gZ1), ptr(gY), B, D, m1, R2 * m3, Cout, s), "spectral3d dft_h (D, bwd)")
-        check(lib.nps_spectral_mix_bwd(ptr(X3), ptr(wpack), ptr(gY), ptr(gX3), ptr(gwp), B, R1, R2 * m3, Cin, Cout,
-                                       s), "spectral3d mix_bwd")
-        dx = None
-        gws = [None] * 4
-        if ctx.needs_input_grad[1]:
-            gX2 = torch.empty((B, D, R2 * m3, Cin), dtype=c64, device=dev)
-            gX1 = torch.empty((B * D, H, m3, Cin), dtype=c64, device=dev)
-            check(lib.nps_spectral_idft_h(ptr(gX3), ptr(gX2), B, D, m1, R2 * m3, Cin, s), "spectral3d idft_h (D, bwd)")
-            check(lib.nps_spectral_idft_h(ptr(gX2), ptr(gX1), B * D, H, m2, m3, Cin, s), "spectral3d idft_h (H, bwd)")
-            dx = torch.empty((B, Cin, D, H, W), dtype=torch.float32, device=dev)
-            check(lib.nps_spectral_dft_w_bwd_nchw(ptr(gX1), ptr(dx), 0, B, D * H, W, m3, Cin, s),
-                  "spectral3d dft_w_bwd_nchw")
-        if any(ctx.needs_input_grad[2:6]):
-            gws = [torch.empty((Cin, Cout, m1, m2, m3), dtype=c64, device=dev) for _ in range(4)]
-            check(lib.nps_spectral3d_unpack_grad(ptr(gwp), *[ptr(g) for g in gws], Cin, Cout, D, H, m1, m2, m3, s),
-                  "spectral3d_unpack_grad")
-        return (None, dx, *gws, None)
-
-
-def spectral_conv3d_nchw(module, x):
-    """x: (B, Cin, D, H, W) -> (B, Cout, D, H, W)."""
-    D, H = x.shape[2], x.shape[3]
-    return SpectralConv3dNchwFn.apply((module.modes1, module.modes2, module.modes3, module.out_channels), x,
-                                      module.weights1, module.weights2, module.weights3, module.weights4,
-                                      module.packed(D, H))
+    return SpectralConv1dFn.apply((module.modes1, module.out_channels, int(module.transform_mode)), x,
+                                  module.weights1, module.packed(), p, module.weights_feat.weight,
+                                  module.weights_feat.bias)
 
 
 # ------------------------------------------------------------------------- decoder / wrapper / loss

@@ -763,20 +763,25 @@ def ctypes_byref(x):
 
 
 # --------------------------------------------------------------- spectral -----
-def film_scale(film, B: int, Cout: int, H: int, m1: int, m2: int) -> torch.Tensor:
-    """The FiLM factor S (B, R, m2, Cout) fp32 of the retained modes (proc_fno.py:271-284; include/nps.h,
-    nps_spectral_film_scale) from film = (p (B, K), weights_feat.weight (Cout*2*m1*m2, K), weights_feat.bias,
-    transform_mode)."""
+def _film_operands(film, B: int, N: int):
+    """film = (p (B, K), weights_feat.weight (N, K), weights_feat.bias (N,), transform_mode) checked (fp32 device
+    tensors of these shapes) and returned detached and contiguous."""
     p, Wf, bf, mode = film
     for t in (p, Wf, bf):
         ptr(t)  # no CPU path
         if t.dtype != torch.float32:
             raise TypeError(f"FiLM operands are fp32 tensors, got {t.dtype}")
-    N = Cout * 2 * m1 * m2
     if p.dim() != 2 or p.shape[0] != B or tuple(Wf.shape) != (N, p.shape[1]) or tuple(bf.shape) != (N,):
         raise ValueError(f"FiLM shapes: p (B={B}, K), weights_feat.weight ({N}, K), bias ({N},); got "
                          f"{tuple(p.shape)}, {tuple(Wf.shape)}, {tuple(bf.shape)}")
-    p, Wf, bf = p.detach().contiguous(), Wf.detach().contiguous(), bf.detach().contiguous()
+    return p.detach().contiguous(), Wf.detach().contiguous(), bf.detach().contiguous(), mode
+
+
+def film_scale(film, B: int, Cout: int, H: int, m1: int, m2: int) -> torch.Tensor:
+    """The FiLM factor S (B, R, m2, Cout) fp32 of the retained modes (proc_fno.py:271-284; include/nps.h,
+    nps_spectral_film_scale) from film = (p (B, K), weights_feat.weight (Cout*2*m1*m2, K), weights_feat.bias,
+    transform_mode)."""
+    p, Wf, bf, mode = _film_operands(film, B, Cout * 2 * m1 * m2)
     S = torch.empty((B, min(H, 2 * m1), m2, Cout), dtype=torch.float32, device=p.device)
     check(lib.nps_spectral_film_scale(ptr(p), ptr(Wf), ptr(bf), ptr(S), B, p.shape[1], Cout, H, m1, m2, int(mode),
                                       stream_ptr()), "spectral_film_scale")
@@ -792,29 +797,132 @@ def spectral_mix(X2, wpack, Y, B, R, m2, Cin, Cout, S=None):
               "spectral_mix_scaled")
 
 
-def spectral_z(srcs: Sequence[Src], wpack: torch.Tensor, m1: int, m2: int, Cout: int, film=None) -> torch.Tensor:
-    """Z (B, H, m2, Cout) complex64: the spectral conv up to its W-pass synthesis (rfft2 W and H passes on the
-    retained modes, the mode mixing, the inverse H pass; proc_fno.py:257-288) — spectral_conv2d's idft_w input, or the
-    spec_z a 1x1 conv's epilogue synthesises itself (conv2d(spec=...), the FNO layer fusion).  film = (p, Wf, bf,
-    transform_mode): FiLM conditioning of the mixed modes (film_scale)."""
-    t0 = srcs[0].t
-    B, H, W = t0.shape[0], t0.shape[1], t0.shape[2]
-    Cin = sum(s.t.shape[3] for s in srcs)
+# The W passes are the only stages of a spectral conv that see the activation layout (csrc/spectral_abi.hip: Lay and
+# w_dft ... w_dft_bwd).  One adapter per layout issues them; spectral2d_fwd / spectral3d_fwd here and the backward
+# chains of autograd.py hold the stage order once and take an adapter.  `dims` is (B, H, W, Cin) of the input as the
+# W pass sees it (H = D*H rows in 3-D); the backward passes need no input, so they hang off the class.
+class NhwcW:
+    """fp32 NHWC sources covering a virtual frame (Sequence[Src])."""
+    out_dtype = torch.float32
+
+    def __init__(self, srcs: Sequence[Src]):
+        t0 = srcs[0].t
+        self.srcs, self.device = srcs, t0.device
+        self.dims = (t0.shape[0], t0.shape[1], t0.shape[2], sum(s.t.shape[3] for s in srcs))
+
+    @classmethod
+    def of(cls, x: torch.Tensor):
+        """The adapter of one whole tensor (the autograd Functions' input)."""
+        return cls([Src(x.contiguous())])
+
+    def new_out(self, Cout):
+        B, H, W, _ = self.dims
+        return torch.empty((B, H, W, Cout), dtype=self.out_dtype, device=self.device)
+
+    def dft_w(self, m, X1):
+        B, H, W, Cin = self.dims
+        check(lib.nps_spectral_dft_w(_c_src(self.srcs), len(self.srcs), B, H, W, Cin, m, ptr(X1), stream_ptr()),
+              "spectral_dft_w")
+
+    def idft_w(self, Z, out, m, Cout, accumulate=False, act=0, addend=None):
+        """out (= or +=) act(W synthesis of Z + addend); raises out's range tag (a fresh one on a new tensor)."""
+        B, H, W, _ = self.dims
+        check(lib.nps_spectral_idft_w(ptr(Z), ptr(out), B, H, W, m, Cout, 1 if accumulate else 0, ptr(addend), act,
+                                      out_tag(out, accumulate), stream_ptr()), "spectral_idft_w")
+
+    @staticmethod
+    def idft_w_bwd(gy, gZ, B, H, W, m, Cout):
+        check(lib.nps_spectral_idft_w_bwd(ptr(gy.contiguous()), ptr(gZ), B, H, W, m, Cout, stream_ptr()),
+              "spectral_idft_w_bwd")
+
+    @staticmethod
+    def dft_w_bwd(gX1, B, H, W, m, Cin):
+        dx = torch.empty((B, H, W, Cin), dtype=torch.float32, device=gX1.device)
+        check(lib.nps_spectral_dft_w_bwd(ptr(gX1), ptr(dx), B, H, W, m, Cin, stream_ptr()), "spectral_dft_w_bwd")
+        return dx
+
+
+class NchwW:
+    """One fp32 channels-first tensor (B, C, *spatial), read as it lies with its batch stride (channels_first)."""
+
+    def __init__(self, x: torch.Tensor):
+        self.x, self.x_bs = channels_first(x)
+        B, Cin, W = self.x.shape[0], self.x.shape[1], self.x.shape[-1]
+        self.device = self.x.device
+        self.dims = (B, self.x[0, 0].numel() // W, W, Cin)
+
+    @classmethod
+    def of(cls, x: torch.Tensor):
+        return cls(x)
+
+    def new_out(self, Cout):
+        return torch.empty((self.x.shape[0], Cout) + tuple(self.x.shape[2:]), dtype=torch.float32, device=self.device)
+
+    def dft_w(self, m, X1):
+        B, H, W, Cin = self.dims
+        check(lib.nps_spectral_dft_w_nchw(ptr(self.x), self.x_bs, B, H, W, Cin, m, ptr(X1), stream_ptr()),
+              "spectral_dft_w_nchw")
+
+    def idft_w(self, Z, out, m, Cout, accumulate=False, act=0, out_bs=0):
+        B, H, W, _ = self.dims
+        check(lib.nps_spectral_idft_w_nchw(ptr(Z), ptr(out), out_bs, B, H, W, m, Cout, 1 if accumulate else 0, act,
+                                           stream_ptr()), "spectral_idft_w_nchw")
+
+    @staticmethod
+    def idft_w_bwd(gy, gZ, B, H, W, m, Cout):
+        gy, gy_bs = channels_first(gy)
+        check(lib.nps_spectral_idft_w_bwd_nchw(ptr(gy), gy_bs, ptr(gZ), B, H, W, m, Cout, stream_ptr()),
+              "spectral_idft_w_bwd_nchw")
+
+    @staticmethod
+    def dft_w_bwd(gX1, B, H, W, m, Cin):
+        dx = torch.empty((B, Cin, H, W), dtype=torch.float32, device=gX1.device)
+        check(lib.nps_spectral_dft_w_bwd_nchw(ptr(gX1), ptr(dx), 0, B, H, W, m, Cin, stream_ptr()),
+              "spectral_dft_w_bwd_nchw")
+        return dx
+
+
+class Bf16W(NhwcW):
+    """bf16 NHWC sources and output, fp32 spectra; forward only."""
+    out_dtype = torch.bfloat16
+    idft_w_bwd = dft_w_bwd = None
+
+    def dft_w(self, m, X1):
+        B, H, W, Cin = self.dims
+        check(lib.nps_spectral_dft_w_bf16(_c_src_bf16(self.srcs), len(self.srcs), B, H, W, Cin, m, ptr(X1),
+                                          stream_ptr()), "spectral_dft_w_bf16")
+
+    def idft_w(self, Z, out, m, Cout, accumulate=False, act=0, addend=None):
+        B, H, W, _ = self.dims
+        check(lib.nps_spectral_idft_w_bf16(ptr(Z), ptr(out), B, H, W, m, Cout, 1 if accumulate else 0, ptr(addend),
+                                           act, stream_ptr()), "spectral_idft_w_bf16")
+
+
+def spectral2d_fwd(lay, wpack: torch.Tensor, m1: int, m2: int, Cout: int, film=None):
+    """The SpectralConv2d forward up to its W-pass synthesis (proc_fno.py:257-288): W and H analysis on the retained
+    modes, the mode mixing (times the FiLM factor of film = (p, Wf, bf, transform_mode), film_scale), the inverse H
+    pass.  Returns (X2 (B, R, m2, Cin) kept for the backward, Z (B, H, m2, Cout) for lay.idft_w, S or None)."""
+    B, H, W, Cin = lay.dims
     if not (m1 <= H and m2 <= W // 2 + 1):
         raise AssertionError("modes should be at most the spatial dim (// 2 + 1 for the last spatial dimension)")
-    R = min(H, 2 * m1)
-    dev = t0.device
-    X1 = torch.empty((B, H, m2, Cin), dtype=torch.complex64, device=dev)
-    X2 = torch.empty((B, R, m2, Cin), dtype=torch.complex64, device=dev)
-    Y = torch.empty((B, R, m2, Cout), dtype=torch.complex64, device=dev)
-    Z = torch.empty((B, H, m2, Cout), dtype=torch.complex64, device=dev)
     S = film_scale(film, B, Cout, H, m1, m2) if film is not None else None
+    R = min(H, 2 * m1)
+    X1 = torch.empty((B, H, m2, Cin), dtype=torch.complex64, device=lay.device)
+    X2 = torch.empty((B, R, m2, Cin), dtype=torch.complex64, device=lay.device)
+    Y = torch.empty((B, R, m2, Cout), dtype=torch.complex64, device=lay.device)
+    Z = torch.empty((B, H, m2, Cout), dtype=torch.complex64, device=lay.device)
     s = stream_ptr()
-    check(lib.nps_spectral_dft_w(_c_src(srcs), len(srcs), B, H, W, Cin, m2, ptr(X1), s), "spectral_dft_w")
+    lay.dft_w(m2, X1)
     check(lib.nps_spectral_dft_h(ptr(X1), ptr(X2), B, H, m1, m2, Cin, s), "spectral_dft_h")
     spectral_mix(X2, wpack, Y, B, R, m2, Cin, Cout, S)
     check(lib.nps_spectral_idft_h(ptr(Y), ptr(Z), B, H, m1, m2, Cout, s), "spectral_idft_h")
-    return Z
+    return X2, Z, S
+
+
+def spectral_z(srcs: Sequence[Src], wpack: torch.Tensor, m1: int, m2: int, Cout: int, film=None) -> torch.Tensor:
+    """Z (B, H, m2, Cout) complex64: the spectral conv up to its W-pass synthesis (spectral2d_fwd) — spectral_conv2d's
+    idft_w input, or the spec_z a 1x1 conv's epilogue synthesises itself (conv2d(spec=...), the FNO layer fusion)."""
+    return spectral2d_fwd(NhwcW(srcs), wpack, m1, m2, Cout, film=film)[1]
 
 
 # the FNO layer's 1x1 `w` synthesises the spectral conv's W pass in its epilogue (nps_conv2d_t.spec_z) instead of a
@@ -830,20 +938,15 @@ def spectral_fusable(W: int, m2: int, Cout: int) -> bool:
 
 def spectral_conv2d(srcs: Sequence[Src], wpack: torch.Tensor, m1: int, m2: int, Cout: int,
                     out: Optional[torch.Tensor] = None, accumulate=False, addend=None, act=0, film=None):
-    """y = irfft2(P(rfft2(x))) on the retained modes (proc_fno.py:257-288), NHWC in/out; film as in spectral_z."""
-    t0 = srcs[0].t
-    B, H, W = t0.shape[0], t0.shape[1], t0.shape[2]
-    Z = spectral_z(srcs, wpack, m1, m2, Cout, film=film)
+    """y = irfft2(P(rfft2(x))) on the retained modes (proc_fno.py:257-288), NHWC in/out; film as in spectral2d_fwd."""
+    lay = NhwcW(srcs)
+    Z = spectral2d_fwd(lay, wpack, m1, m2, Cout, film=film)[1]
     if out is not None:
         drop_stats(out)
     if out is None:
-        out = empty_nhwc(B, H, W, Cout, t0)
+        out = lay.new_out(Cout)
         accumulate = False
-        tag = new_tag(out)
-    else:
-        tag = out_tag(out, accumulate)
-    check(lib.nps_spectral_idft_w(ptr(Z), ptr(out), B, H, W, m2, Cout, 1 if accumulate else 0, ptr(addend), act,
-                                  tag, stream_ptr()), "spectral_idft_w")
+    lay.idft_w(Z, out, m2, Cout, accumulate, act, addend)
     return out
 
 
@@ -911,16 +1014,7 @@ def spectral1d_idft(Z: torch.Tensor, L: int, out: Optional[torch.Tensor] = None,
 def film1d_scale(film, B: int, Cout: int, m: int) -> torch.Tensor:
     """The FiLM factor S (B, m, Cout) fp32 (proc_fno.py:209-218) from film = (p (B, K), weights_feat.weight
     (Cout*m, K), weights_feat.bias, transform_mode)."""
-    p, Wf, bf, mode = film
-    for t in (p, Wf, bf):
-        ptr(t)  # no CPU path
-        if t.dtype != torch.float32:
-            raise TypeError(f"FiLM operands are fp32 tensors, got {t.dtype}")
-    N = Cout * m
-    if p.dim() != 2 or p.shape[0] != B or tuple(Wf.shape) != (N, p.shape[1]) or tuple(bf.shape) != (N,):
-        raise ValueError(f"FiLM shapes: p (B={B}, K), weights_feat.weight ({N}, K), bias ({N},); got "
-                         f"{tuple(p.shape)}, {tuple(Wf.shape)}, {tuple(bf.shape)}")
-    p, Wf, bf = p.detach().contiguous(), Wf.detach().contiguous(), bf.detach().contiguous()
+    p, Wf, bf, mode = _film_operands(film, B, Cout * m)
     S = torch.empty((B, m, Cout), dtype=torch.float32, device=p.device)
     check(lib.nps_spectral1d_film_scale(ptr(p), ptr(Wf), ptr(bf), ptr(S), B, p.shape[1], Cout, m, int(mode),
                                         stream_ptr()), "spectral1d_film_scale")
@@ -963,13 +1057,16 @@ def check_modes3d(D, H, W, m1, m2, m3):
         raise AssertionError("modes should be at most the spatial dim (// 2 + 1 for the last spatial dimension)")
 
 
-def spectral_conv3d_stages(x4: Sequence[Src], D, H, W, Cin, wpack, m1, m2, m3, Cout, out, accumulate=False,
-                           addend=None, act=0):
-    """The SpectralConv3d forward chain on a virtual NDHWC frame given as (B, D*H, W, C) sources.
-    Returns the X3 spectrum (kept for the backward)."""
-    B = x4[0].t.shape[0]
+def spectral3d_fwd(lay, D: int, wpack, m1, m2, m3, Cout, out, accumulate=False, act=0, mix=lib.nps_spectral_mix,
+                   **last):
+    """The SpectralConv3d forward chain (proc_fno.py:334-376), axis by axis with the 2-D kernels, on a (B, D, H, W)
+    volume whose W passes `lay` issues on D*H rows; `mix` is the mixer of wpack's dtype, `last` what lay.idft_w takes
+    beyond (accumulate, act).  Writes `out`; returns the X3 spectrum (kept for the backward)."""
+    B, DH, W, Cin = lay.dims
+    H = DH // D
+    check_modes3d(D, H, W, m1, m2, m3)
     R1, R2 = min(D, 2 * m1), min(H, 2 * m2)
-    dev = x4[0].t.device
+    dev = lay.device
     c64 = torch.complex64
     X1 = torch.empty((B, D * H, m3, Cin), dtype=c64, device=dev)
     X2 = torch.empty((B * D, R2, m3, Cin), dtype=c64, device=dev)
@@ -978,33 +1075,33 @@ def spectral_conv3d_stages(x4: Sequence[Src], D, H, W, Cin, wpack, m1, m2, m3, C
     Z1 = torch.empty((B, D, R2 * m3, Cout), dtype=c64, device=dev)
     Z2 = torch.empty((B * D, H, m3, Cout), dtype=c64, device=dev)
     s = stream_ptr()
-    check(lib.nps_spectral_dft_w(_c_src(x4), len(x4), B, D * H, W, Cin, m3, ptr(X1), s), "spectral3d dft_w")
+    lay.dft_w(m3, X1)
     check(lib.nps_spectral_dft_h(ptr(X1), ptr(X2), B * D, H, m2, m3, Cin, s), "spectral3d dft_h (H)")
     check(lib.nps_spectral_dft_h(ptr(X2), ptr(X3), B, D, m1, R2 * m3, Cin, s), "spectral3d dft_h (D)")
-    check(lib.nps_spectral_mix(ptr(X3), ptr(wpack), ptr(Y), B, R1, R2 * m3, Cin, Cout, s), "spectral3d mix")
+    check(mix(ptr(X3), ptr(wpack), ptr(Y), B, R1, R2 * m3, Cin, Cout, s), "spectral3d mix")
     check(lib.nps_spectral_idft_h(ptr(Y), ptr(Z1), B, D, m1, R2 * m3, Cout, s), "spectral3d idft_h (D)")
     check(lib.nps_spectral_idft_h(ptr(Z1), ptr(Z2), B * D, H, m2, m3, Cout, s), "spectral3d idft_h (H)")
-    check(lib.nps_spectral_idft_w(ptr(Z2), ptr(out), B, D * H, W, m3, Cout, 1 if accumulate else 0, ptr(addend), act,
-                                  out_tag(out, accumulate), s), "spectral3d idft_w")
+    lay.idft_w(Z2, out, m3, Cout, accumulate, act, **last)
     return X3
+
+
+def _spectral_conv3d(lay, mix, D, wpack, m1, m2, m3, Cout, out, accumulate, addend, act):
+    """spectral_conv3d / _bf16 on their adapter: NHWC out handling around spectral3d_fwd."""
+    if out is not None:
+        drop_stats(out)
+    if out is None:
+        out = lay.new_out(Cout)
+        accumulate = False
+    spectral3d_fwd(lay, D, wpack, m1, m2, m3, Cout, out, accumulate, act, mix=mix, addend=addend)
+    return out
 
 
 def spectral_conv3d(srcs: Sequence[Src], D: int, wpack: torch.Tensor, m1: int, m2: int, m3: int, Cout: int,
                     out: Optional[torch.Tensor] = None, accumulate=False, addend=None, act=0):
     """y = irfftn(P(rfftn(x))) on the 4 retained corners (proc_fno.py:334-376).  Sources are NDHWC
     tensors viewed as (B, D*H, W, C); returns (B, D*H, W, Cout) (view it as (B, D, H, W, Cout))."""
-    t0 = srcs[0].t
-    B, DH, W = t0.shape[0], t0.shape[1], t0.shape[2]
-    H = DH // D
-    Cin = sum(s.t.shape[3] for s in srcs)
-    check_modes3d(D, H, W, m1, m2, m3)
-    if out is not None:
-        drop_stats(out)
-    if out is None:
-        out = empty_nhwc(B, DH, W, Cout, t0)
-        accumulate = False
-    spectral_conv3d_stages(srcs, D, H, W, Cin, wpack, m1, m2, m3, Cout, out, accumulate, addend, act)
-    return out
+    return _spectral_conv3d(NhwcW(srcs), lib.nps_spectral_mix, D, wpack, m1, m2, m3, Cout, out, accumulate, addend,
+                            act)
 
 
 # ------------------------------------------------- channels-first spectral convs -----
@@ -1031,82 +1128,27 @@ def _out_channels_first(out, shape, like):
     return out, obs, True
 
 
-def spectral_mid2d(X1, wpack, B, H, m1, m2, Cin, Cout, film=None):
-    """The layout-independent middle of SpectralConv2d: X1 -> (X2 kept for the backward, Z), or with film = (p, Wf,
-    bf, transform_mode) -> (X2, Z, S): the FiLM factor S (film_scale) multiplies the mixed modes and is kept too."""
-    R = min(H, 2 * m1)
-    dev = X1.device
-    X2 = torch.empty((B, R, m2, Cin), dtype=torch.complex64, device=dev)
-    Y = torch.empty((B, R, m2, Cout), dtype=torch.complex64, device=dev)
-    Z = torch.empty((B, H, m2, Cout), dtype=torch.complex64, device=dev)
-    S = film_scale(film, B, Cout, H, m1, m2) if film is not None else None
-    s = stream_ptr()
-    check(lib.nps_spectral_dft_h(ptr(X1), ptr(X2), B, H, m1, m2, Cin, s), "spectral_dft_h")
-    spectral_mix(X2, wpack, Y, B, R, m2, Cin, Cout, S)
-    check(lib.nps_spectral_idft_h(ptr(Y), ptr(Z), B, H, m1, m2, Cout, s), "spectral_idft_h")
-    return (X2, Z) if film is None else (X2, Z, S)
-
-
-def spectral_conv2d_nchw_stages(x, x_bs, wpack, m1, m2, Cout, out, out_bs, accumulate=False, act=0, film=None):
-    """SpectralConv2d forward chain reading x and writing out channels-first.  Returns X2 (kept for the backward), or
-    (X2, S) with film (spectral_mid2d)."""
-    B, Cin, H, W = x.shape
-    if not (m1 <= H and m2 <= W // 2 + 1):
-        raise AssertionError("modes should be at most the spatial dim (// 2 + 1 for the last spatial dimension)")
-    X1 = torch.empty((B, H, m2, Cin), dtype=torch.complex64, device=x.device)
-    s = stream_ptr()
-    check(lib.nps_spectral_dft_w_nchw(ptr(x), x_bs, B, H, W, Cin, m2, ptr(X1), s), "spectral_dft_w_nchw")
-    X2, Z, *S = spectral_mid2d(X1, wpack, B, H, m1, m2, Cin, Cout, film=film)
-    check(lib.nps_spectral_idft_w_nchw(ptr(Z), ptr(out), out_bs, B, H, W, m2, Cout, 1 if accumulate else 0, act, s),
-          "spectral_idft_w_nchw")
-    return X2 if film is None else (X2, S[0])
-
-
 def spectral_conv2d_nchw(x: torch.Tensor, wpack: torch.Tensor, m1: int, m2: int, Cout: int,
                          out: Optional[torch.Tensor] = None, accumulate=False, act=0, film=None):
     """y = irfft2(P(rfft2(x))) on the retained modes (proc_fno.py:257-288), NCHW in / out with no transpose: x
     (B, Cin, H, W) -> (B, Cout, H, W); out (= or +=, then act) may be a channel slice of a larger tensor; film as in
-    spectral_z."""
-    x, x_bs = channels_first(x)
-    B, _, H, W = x.shape
-    out, out_bs, given = _out_channels_first(out, (B, Cout, H, W), x)
-    spectral_conv2d_nchw_stages(x, x_bs, wpack, m1, m2, Cout, out, out_bs, accumulate and given, act, film=film)
+    spectral2d_fwd."""
+    lay = NchwW(x)
+    B, H, W, _ = lay.dims
+    out, out_bs, given = _out_channels_first(out, (B, Cout, H, W), lay.x)
+    Z = spectral2d_fwd(lay, wpack, m1, m2, Cout, film=film)[1]
+    lay.idft_w(Z, out, m2, Cout, accumulate and given, act, out_bs)
     return out
-
-
-def spectral_conv3d_nchw_stages(x, x_bs, wpack, m1, m2, m3, Cout, out, out_bs, accumulate=False, act=0):
-    """SpectralConv3d forward chain on NCDHW x / out (viewed as (B, C, D*H, W)).  Returns X3 (kept for the backward)."""
-    B, Cin, D, H, W = x.shape
-    check_modes3d(D, H, W, m1, m2, m3)
-    R1, R2 = min(D, 2 * m1), min(H, 2 * m2)
-    dev = x.device
-    c64 = torch.complex64
-    X1 = torch.empty((B, D * H, m3, Cin), dtype=c64, device=dev)
-    X2 = torch.empty((B * D, R2, m3, Cin), dtype=c64, device=dev)
-    X3 = torch.empty((B, R1, R2 * m3, Cin), dtype=c64, device=dev)
-    Y = torch.empty((B, R1, R2 * m3, Cout), dtype=c64, device=dev)
-    Z1 = torch.empty((B, D, R2 * m3, Cout), dtype=c64, device=dev)
-    Z2 = torch.empty((B * D, H, m3, Cout), dtype=c64, device=dev)
-    s = stream_ptr()
-    check(lib.nps_spectral_dft_w_nchw(ptr(x), x_bs, B, D * H, W, Cin, m3, ptr(X1), s), "spectral3d dft_w_nchw")
-    check(lib.nps_spectral_dft_h(ptr(X1), ptr(X2), B * D, H, m2, m3, Cin, s), "spectral3d dft_h (H)")
-    check(lib.nps_spectral_dft_h(ptr(X2), ptr(X3), B, D, m1, R2 * m3, Cin, s), "spectral3d dft_h (D)")
-    check(lib.nps_spectral_mix(ptr(X3), ptr(wpack), ptr(Y), B, R1, R2 * m3, Cin, Cout, s), "spectral3d mix")
-    check(lib.nps_spectral_idft_h(ptr(Y), ptr(Z1), B, D, m1, R2 * m3, Cout, s), "spectral3d idft_h (D)")
-    check(lib.nps_spectral_idft_h(ptr(Z1), ptr(Z2), B * D, H, m2, m3, Cout, s), "spectral3d idft_h (H)")
-    check(lib.nps_spectral_idft_w_nchw(ptr(Z2), ptr(out), out_bs, B, D * H, W, m3, Cout, 1 if accumulate else 0, act,
-                                       s), "spectral3d idft_w_nchw")
-    return X3
 
 
 def spectral_conv3d_nchw(x: torch.Tensor, wpack: torch.Tensor, m1: int, m2: int, m3: int, Cout: int,
                          out: Optional[torch.Tensor] = None, accumulate=False, act=0):
     """y = irfftn(P(rfftn(x))) on the 4 retained corners (proc_fno.py:334-376), NCDHW in / out with no transpose:
     x (B, Cin, D, H, W) -> (B, Cout, D, H, W)."""
-    x, x_bs = channels_first(x)
-    B, _, D, H, W = x.shape
-    out, out_bs, given = _out_channels_first(out, (B, Cout, D, H, W), x)
-    spectral_conv3d_nchw_stages(x, x_bs, wpack, m1, m2, m3, Cout, out, out_bs, accumulate and given, act)
+    lay = NchwW(x)
+    B, _, D, H, W = lay.x.shape
+    out, out_bs, given = _out_channels_first(out, (B, Cout, D, H, W), lay.x)
+    spectral3d_fwd(lay, D, wpack, m1, m2, m3, Cout, out, accumulate and given, act, out_bs=out_bs)
     return out
 
 
@@ -1176,35 +1218,8 @@ def conv1x1_bf16(srcs: Sequence[Src], wpack: torch.Tensor, bias: Optional[torch.
 def spectral_conv3d_bf16(srcs: Sequence[Src], D: int, wpack_bf16: torch.Tensor, m1: int, m2: int, m3: int, Cout: int,
                          out: Optional[torch.Tensor] = None, accumulate=False, addend=None, act=0):
     """spectral_conv3d with bf16 activations in / out and bf16 packed weights (fp32 spectra and sums)."""
-    t0 = srcs[0].t
-    B, DH, W = t0.shape[0], t0.shape[1], t0.shape[2]
-    H = DH // D
-    Cin = sum(s.t.shape[3] for s in srcs)
-    check_modes3d(D, H, W, m1, m2, m3)
-    if out is not None:
-        drop_stats(out)
-    if out is None:
-        out = torch.empty((B, DH, W, Cout), dtype=torch.bfloat16, device=t0.device)
-        accumulate = False
-    R1, R2 = min(D, 2 * m1), min(H, 2 * m2)
-    dev = t0.device
-    c64 = torch.complex64
-    X1 = torch.empty((B, D * H, m3, Cin), dtype=c64, device=dev)
-    X2 = torch.empty((B * D, R2, m3, Cin), dtype=c64, device=dev)
-    X3 = torch.empty((B, R1, R2 * m3, Cin), dtype=c64, device=dev)
-    Y = torch.empty((B, R1, R2 * m3, Cout), dtype=c64, device=dev)
-    Z1 = torch.empty((B, D, R2 * m3, Cout), dtype=c64, device=dev)
-    Z2 = torch.empty((B * D, H, m3, Cout), dtype=c64, device=dev)
-    s = stream_ptr()
-    check(lib.nps_spectral_dft_w_bf16(_c_src_bf16(srcs), len(srcs), B, D * H, W, Cin, m3, ptr(X1), s), "dft_w bf16")
-    check(lib.nps_spectral_dft_h(ptr(X1), ptr(X2), B * D, H, m2, m3, Cin, s), "spectral3d dft_h (H)")
-    check(lib.nps_spectral_dft_h(ptr(X2), ptr(X3), B, D, m1, R2 * m3, Cin, s), "spectral3d dft_h (D)")
-    check(lib.nps_spectral_mix_bf16(ptr(X3), ptr(wpack_bf16), ptr(Y), B, R1, R2 * m3, Cin, Cout, s), "mix bf16")
-    check(lib.nps_spectral_idft_h(ptr(Y), ptr(Z1), B, D, m1, R2 * m3, Cout, s), "spectral3d idft_h (D)")
-    check(lib.nps_spectral_idft_h(ptr(Z1), ptr(Z2), B * D, H, m2, m3, Cout, s), "spectral3d idft_h (H)")
-    check(lib.nps_spectral_idft_w_bf16(ptr(Z2), ptr(out), B, D * H, W, m3, Cout, 1 if accumulate else 0, ptr(addend),
-                                       act, s), "idft_w bf16")
-    return out
+    return _spectral_conv3d(Bf16W(srcs), lib.nps_spectral_mix_bf16, D, wpack_bf16, m1, m2, m3, Cout, out, accumulate,
+                            addend, act)
 
 
 # ------------------------------------------------------------ 3-D U-Net (C5) -----

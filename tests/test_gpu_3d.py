@@ -52,6 +52,34 @@ def test_spectral3d_backward_golden(name):
         assert rel_l2(_r(gw), _r(g["dw"][i])) < TOL, f"weights{i + 1}"
 
 
+@pytest.mark.parametrize("nchw", [False, True], ids=["ndhwc", "ncdhw"])
+@pytest.mark.parametrize("want", ["weights", "input"])
+def test_spectral3d_backward_partial_gradients(want, nchw):
+    """nps_hip.autograd.spectral_conv3d / spectral_conv3d_nchw with only some gradients requested, on the
+    overlapping-corners fixture: weights only (x frozen: no dx), input only (weights frozen: dx and no weight
+    gradient)."""
+    from nps_hip import autograd as ad
+    g = load_golden("spectral3d_overlap")
+    m = _spectral3d(g).requires_grad_(want == "weights")
+    B, C, D, H, W = g["x"].shape
+
+    def lay(t):  # NCDHW -> the (B, D*H, W, C) view of NDHWC
+        return t if nchw else t.permute(0, 2, 3, 4, 1).reshape(B, D * H, W, t.shape[1]).contiguous()
+
+    x = lay(g["x"]).to(DEV).requires_grad_(want == "input")
+    y = ad.spectral_conv3d_nchw(m, x) if nchw else ad.spectral_conv3d(m, x, D)
+    y.backward(lay(g["g"]).to(DEV))
+    if want == "weights":
+        assert x.grad is None
+        for i in range(4):
+            gw = getattr(m, f"weights{i + 1}").grad.cpu()
+            assert rel_l2(_r(gw), _r(g["dw"][i])) < TOL, f"weights{i + 1}"
+    else:
+        assert all(prm.grad is None for prm in m.parameters())
+        dx = x.grad.cpu()
+        assert rel_l2(dx if nchw else dx.reshape(B, D, H, W, C).permute(0, 4, 1, 2, 3), g["dx"]) < TOL
+
+
 def _fno3d(g):
     from models.enc_proc_dec_components.proc_fno import FNO
     kw = dict(g["kwargs"])

@@ -264,6 +264,28 @@ def test_spectral2d_backward_golden(name):
     assert rel_l2(m.weights2.grad, g["dw2"]) < TOL
 
 
+@pytest.mark.parametrize("want", ["weights", "input"])
+def test_spectral2d_backward_partial_gradients(want):
+    """nps_hip.autograd.spectral_conv2d (NHWC) with only some gradients requested, on the overlapping-corners
+    fixture: weights only (x frozen: no dx), input only (weights frozen: dx and no weight gradient)."""
+    from models.enc_proc_dec_components.proc_fno import SpectralConv2d
+    from nps_hip import autograd as ad
+    g = load_golden("spectral2d_overlap")
+    kw = g["kwargs"]
+    m = SpectralConv2d(kw["in_channels"], kw["out_channels"], tuple(kw["modes"]))
+    m.load_state_dict(g["state_dict"])
+    m = m.to(DEV).requires_grad_(want == "weights")
+    x = g["x"].permute(0, 2, 3, 1).contiguous().to(DEV).requires_grad_(want == "input")
+    ad.spectral_conv2d(m, x).backward(g["g"].permute(0, 2, 3, 1).contiguous().to(DEV))
+    if want == "weights":
+        assert x.grad is None
+        assert rel_l2(m.weights1.grad, g["dw1"]) < TOL
+        assert rel_l2(m.weights2.grad, g["dw2"]) < TOL
+    else:
+        assert m.weights1.grad is None and m.weights2.grad is None
+        assert rel_l2(x.grad.permute(0, 3, 1, 2), g["dx"]) < TOL
+
+
 @pytest.mark.parametrize("H,W,m", [(64, 64, 12), (96, 64, 10)])
 def test_spectral2d_backward_full_channels(H, W, m):
     from models.enc_proc_dec_components.proc_fno import SpectralConv2d

@@ -83,6 +83,29 @@ def test_fixture_through_the_nhwc_run_ad_route(name):
     _check_grads(m, g, name + " (NHWC)")
 
 
+@pytest.mark.parametrize("nchw", [False, True], ids=["nhwc", "nchw"])
+@pytest.mark.parametrize("want", ["weights", "input"])
+def test_partial_gradients_on_the_overlap_fixture(want, nchw):
+    """nps_hip.autograd.spectral_conv2d_film(_nchw) with only some gradients requested: weights only (weights1/2 and
+    weights_feat; x and p frozen: no dx, no dp), input only (parameters frozen: dx, dp and no parameter gradient)."""
+    from nps_hip import autograd as ad
+    name = "spectral2d_overlap_tm1"
+    m, g = _module(name)
+    m.requires_grad_(want == "weights")
+    lay = (lambda t: t) if nchw else _nhwc
+    x = lay(g["x"]).to(DEV).requires_grad_(want == "input")
+    p = g["p"].to(DEV).requires_grad_(want == "input")
+    fn = ad.spectral_conv2d_film_nchw if nchw else ad.spectral_conv2d_film
+    fn(m, x, p).backward(lay(g["g"]).to(DEV))
+    if want == "weights":
+        assert x.grad is None and p.grad is None
+        _check_grads(m, g, f"{name} (weights only)")
+    else:
+        assert all(prm.grad is None for prm in m.parameters())
+        assert rel_l2(x.grad if nchw else x.grad.permute(0, 3, 1, 2), g["dx"]) < TOL
+        assert rel_l2(p.grad, g["dp"]) < TOL
+
+
 # ------------------------------------------------------------------ mixer paths the fixture misses
 H_, W_, M1_, M2_ = 8, 10, 3, 4
 # (B, Cin, Cout, K): MFMA mixer with NBC = 2, a batch tail, a second input-channel chunk and a partial second

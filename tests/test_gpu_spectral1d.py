@@ -102,6 +102,28 @@ def test_fixture_through_the_channels_last_run_ad_route(name):
     _check_grads(m, g, name + " (channels-last)")
 
 
+@pytest.mark.parametrize("name", ["spectral1d_odd", "spectral1d_odd_tm1"])
+@pytest.mark.parametrize("want", ["weights", "input"])
+def test_partial_gradients(want, name):
+    """nps_hip.autograd.spectral_conv1d / spectral_conv1d_film with only some gradients requested: weights only (x
+    and p frozen: no dx, no dp), input only (parameters frozen: dx, dp and no parameter gradient)."""
+    from nps_hip import autograd as ad
+    m, g = _module(name)
+    m.requires_grad_(want == "weights")
+    x = _cl(g["x"]).to(DEV).requires_grad_(want == "input")
+    p = g["p"].to(DEV).requires_grad_(want == "input") if "p" in g else None
+    y = ad.spectral_conv1d(m, x) if p is None else ad.spectral_conv1d_film(m, x, p)
+    y.backward(_cl(g["g"]).to(DEV))
+    if want == "weights":
+        assert x.grad is None and (p is None or p.grad is None)
+        _check_grads(m, g, f"{name} (weights only)")
+    else:
+        assert all(prm.grad is None for prm in m.parameters())
+        _check(f"{name}: dx (input only)", _cf(x.grad), g["dx"])
+        if p is not None:
+            _check(f"{name}: dp (input only)", p.grad, g["dp"])
+
+
 def test_fixture_through_the_channels_last_run_route():
     """The inference `run` of layers and FNO on (B, 1, L, C) views, the two-source frame of cond_mode concat."""
     from nps_hip import ops

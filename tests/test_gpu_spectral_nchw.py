@@ -154,6 +154,28 @@ def test_spectral3d_nchw_golden(name):
             assert rel_l2(dws[i], g["dw"][i]) < TOL, f"weights{i + 1}"
 
 
+@pytest.mark.parametrize("want", ["weights", "input"])
+def test_spectral2d_nchw_autograd_partial_gradients(want):
+    """nps_hip.autograd.spectral_conv2d_nchw with only some gradients requested, on the overlapping-corners fixture:
+    weights only (x frozen: no dx), input only (weights frozen: dx and no weight gradient)."""
+    from models.enc_proc_dec_components.proc_fno import SpectralConv2d
+    from nps_hip import autograd as ad
+    g = load_golden("spectral2d_overlap")
+    kw = g["kwargs"]
+    m = SpectralConv2d(kw["in_channels"], kw["out_channels"], tuple(kw["modes"]))
+    m.load_state_dict(g["state_dict"])
+    m = m.to(DEV).requires_grad_(want == "weights")
+    x = g["x"].to(DEV).requires_grad_(want == "input")
+    ad.spectral_conv2d_nchw(m, x).backward(g["g"].to(DEV))
+    if want == "weights":
+        assert x.grad is None
+        assert rel_l2(m.weights1.grad, g["dw1"]) < TOL
+        assert rel_l2(m.weights2.grad, g["dw2"]) < TOL
+    else:
+        assert m.weights1.grad is None and m.weights2.grad is None
+        assert rel_l2(x.grad, g["dx"]) < TOL
+
+
 # ------------------------------------------------------------------ oracle + autograd
 @functools.lru_cache(maxsize=None)
 def _case2d(B, Cin, Cout, H, W, m1, m2):
