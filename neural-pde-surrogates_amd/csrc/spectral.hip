@@ -291,8 +291,7 @@ __global__ __launch_bounds__(256) void dft_h2_kernel(const float2* __restrict__ 
 
 // H-pass of the inverse DFT: Z[b][h][col] = sum_r Y[b][r][col] e^{+2 pi i k1(r) h / H}.  Work-group = 64
 // columns x IH_HB rows h (4 waves, wave s taking h = h0 + s, + 4, ...), the column's RC retained values in
-// registers, the twiddles of the block's rows in LDS; same r order and fma form as the one-thread-per-column
-// kernel it replaces (bit-identical results, 16x the work-groups).
+// registers, the twiddles of the block's rows in LDS; r is summed in ascending order.
 constexpr int IH_HB = 64;
 template <int RC>
 __global__ __launch_bounds__(256) void idft_h2_kernel(const float2* __restrict__ Y, float2* __restrict__ Z, int H,
@@ -514,32 +513,6 @@ __global__ __launch_bounds__(256) void mix_mfma_kernel(const float2* __restrict_
                 }
             }
         }
-    }
-}
-
-// Z[b][h][k2][o] = sum_r Y[b][r][k2][o] e^{+2 pi i k1(r) h / H}
-__global__ void idft_h_kernel(const float2* __restrict__ Y, float2* __restrict__ Z, int H, int R, int m1, int m2,
-                              int Cout) {
-    extern __shared__ float2 tw[];  // [R][H]
-    const int b = blockIdx.z;
-    for (int i = threadIdx.x; i < R * H; i += blockDim.x) tw[i] = twiddle(row_k1(i / H, H, R, m1), i % H, H);
-    __syncthreads();
-    const int idx = blockIdx.x * blockDim.x + threadIdx.x;  // (k2, o)
-    if (idx >= m2 * Cout) return;
-    float2 y[MAXR];
-#pragma unroll
-    for (int r = 0; r < MAXR; ++r) y[r] = (r < R) ? Y[((size_t)(b * R + r) * m2) * Cout + idx] : make_float2(0.f, 0.f);
-    for (int hh = 0; hh < H; ++hh) {
-        float re = 0.f, im = 0.f;
-#pragma unroll
-        for (int r = 0; r < MAXR; ++r) {
-            if (r < R) {
-                const float2 t = tw[r * H + hh];  // e^{+i th} = (c, s)
-                re = fmaf(y[r].x, t.x, fmaf(-y[r].y, t.y, re));
-                im = fmaf(y[r].x, t.y, fmaf(y[r].y, t.x, im));
-            }
-        }
-        Z[((size_t)(b * H + hh) * m2) * Cout + idx] = make_float2(re, im);
     }
 }
 
@@ -1258,31 +1231,17 @@ extern "C" int nps_spectral_idft_h(const float* Y, float* Z, int B, int H, int m
     NPS_CHECK_ARG(Y && Z && B > 0 && H > 0 && m1 > 0 && m1 <= H && m2 > 0 && Cout > 0, "spectral_idft_h: bad args");
     const int R = H < 2 * m1 ? H : 2 * m1;
     NPS_CHECK_ARG(R <= MAXR, "spectral_idft_h: %d retained rows > %d", R, MAXR);
-    {
-        const int NC = m2 * Cout;
-        const dim3 g2((NC + 63) / 64, (H + IH_HB - 1) / IH_HB, B);
-        hipStream_t s = (hipStream_t)stream;
-        const auto* y = reinterpret_cast<const float2*>(Y);
-        auto* z = reinterpret_cast<float2*>(Z);
-        switch (rc_for(R)) {
-            case 8: idft_h2_kernel<8><<<g2, 256, 0, s>>>(y, z, H, R, m1, NC); break;
-            case 16: idft_h2_kernel<16><<<g2, 256, 0, s>>>(y, z, H, R, m1, NC); break;
-            case 24: idft_h2_kernel<24><<<g2, 256, 0, s>>>(y, z, H, R, m1, NC); break;
-            default: idft_h2_kernel<32><<<g2, 256, 0, s>>>(y, z, H, R, m1, NC); break;
-        }
-        NPS_CHECK_LAUNCH("spectral_idft_h");
-        return 0;
+    const int NC = m2 * Cout;
+    const dim3 g2((NC + 63) / 64, (H + IH_HB - 1) / IH_HB, B);
+    hipStream_t s = (hipStream_t)stream;
+    const auto* y = reinterpret_cast<const float2*>(Y);
+    auto* z = reinterpret_cast<float2*>(Z);
+    switch (rc_for(R)) {
+        case 8: idft_h2_kernel<8><<<g2, 256, 0, s>>>(y, z, H, R, m1, NC); break;
+        case 16: idft_h2_kernel<16><<<g2, 256, 0, s>>>(y, z, H, R, m1, NC); break;
+        case 24: idft_h2_kernel<24><<<g2, 256, 0, s>>>(y, z, H, R, m1, NC); break;
+        default: idft_h2_kernel<32><<<g2, 256, 0, s>>>(y, z, H, R, m1, NC); break;
     }
-    const size_t lds = sizeof(float2) * R * H;
-    NPS_CHECK_ARG(lds <= 96 * 1024, "spectral_idft_h: H=%d too large", H);
-    dim3 grid((m2 * Cout + 255) / 256, 1, B);
-    static bool attr_set = false;
-    if (!attr_set) {
-        (void)hipFuncSetAttribute((const void*)idft_h_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, 96 * 1024);
-        attr_set = true;
-    }
-    idft_h_kernel<<<grid, 256, lds, (hipStream_t)stream>>>(reinterpret_cast<const float2*>(Y),
-                                                           reinterpret_cast<float2*>(Z), H, R, m1, m2, Cout);
     NPS_CHECK_LAUNCH("spectral_idft_h");
     return 0;
 }

@@ -5,12 +5,11 @@ bf16-rounded operands, so that only the kernel's own arithmetic and its one outp
 of whole tensors (rel-L2 5e-3 / 1e-2), which hides truncation instead of round-to-nearest-even, a dropped Nyquist
 rule or a mishandled source tail.
 """
-import math
-
 import pytest
 import torch
 
 from conftest import rel_l2
+from spectral2d_ref import c2r_partial as _c2r_partial
 
 pytestmark = pytest.mark.gpu
 DEV = "cuda"
@@ -89,19 +88,6 @@ def test_spectral_dft_w_bf16_vs_fp64(B, H, W, m2, chans):
 
 
 # ------------------------------------------------------------------ W-pass synthesis
-def _c2r_partial(Z, W, k0, k1, scale):
-    """scale * sum_{k0 <= k < k1} c_k Re(Z[..., k, :] e^{2 pi i k w / W}) -> (B, H, W, Cout) fp64: the one-sided c2r
-    synthesis (DC and, for even W, Nyquist once with their imaginary parts dropped; every other bin twice)."""
-    k = torch.arange(k0, k1, dtype=torch.float64)
-    self_conj = (k == 0) | (2 * k == W)
-    ck = 2.0 - self_conj.double()
-    ang = 2 * math.pi * k[:, None] * torch.arange(W, dtype=torch.float64)[None, :] / W      # (k, w)
-    Zr, Zi = Z.real.double()[:, :, k0:k1], Z.imag.double()[:, :, k0:k1]
-    Zi = Zi * (~self_conj).double()[None, None, :, None]
-    return scale * (torch.einsum("bhko,kw->bhwo", Zr, ck[:, None] * torch.cos(ang)) -
-                    torch.einsum("bhko,kw->bhwo", Zi, ck[:, None] * torch.sin(ang)))
-
-
 @pytest.mark.parametrize("B,H,W,m2,Cout,fused", [
     (2, 5, 24, 12, 64, False),   # C5's kind: one chunk, plain
     (1, 3, 16, 9, 12, True),     # Nyquist; accumulate onto a bf16 out + bf16 addend + GELU
