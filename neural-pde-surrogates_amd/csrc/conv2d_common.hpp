@@ -120,6 +120,10 @@ __device__ __forceinline__ void stats_publish(const nps_conv2d_t& a, int b, doub
 // the same b): the waves' sums meet in `red` (2 doubles per wave of LDS nobody else touches until the caller's
 // next barrier), then one thread adds them — 4-8x fewer fp64 atomics on the 16 sub-slots of a sample, whose
 // contention measured +50 us per 1x1x1 launch in the 3-D convs
+// RAW: the exchange's barrier waits for the LDS writes only (lgkmcnt), not, as __syncthreads() does, for every
+// global store the caller has in flight — for callers whose code after it reads none of the stored values
+// (the split-fp16 ring kernel's store phase).
+template <bool RAW = false>
 __device__ __forceinline__ void stats_publish_wg(const nps_conv2d_t& a, int b, double s1, double s2, double* red) {
     if (a.out_stats == nullptr) return;
     s1 = nps::wave_sum(s1);
@@ -129,7 +133,10 @@ __device__ __forceinline__ void stats_publish_wg(const nps_conv2d_t& a, int b, d
         red[2 * w] = s1;
         red[2 * w + 1] = s2;
     }
-    __syncthreads();
+    if constexpr (RAW)
+        asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory");
+    else
+        __syncthreads();
     if (threadIdx.x == 0) {
         double t1 = 0.0, t2 = 0.0;
         for (int i = 0; i < nw; ++i) {

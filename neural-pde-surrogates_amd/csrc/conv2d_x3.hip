@@ -59,17 +59,128 @@ __host__ __device__ __forceinline__ bool x3_lds_epilogue(const nps_conv2d_t& a) 
     return !a.out_nchw && (a.out_C & 3) == 0 && (a.Cout & 3) == 0;
 }
 
+// Channel quad (0-15, + 16 j for j = 0..2) of thread tid in the fast store phase of a wide tile: the 16 threads
+// [16 p, 16 p + 16) cover the quads of tile pixel p (+ 32 k), rotated by p so that the 16-B LDS slot of a lane's
+// ds_read_b128 of T (pixel pitch 196 floats = 49 slots) is tid mod 16 in every 16-lane group the LDS serves
+// together (conv2d_common.hpp, x3_row_bytes; the unrotated map puts two lanes of every group on one slot).
+// tests/test_x3_store_map.py evaluates this map under the lane-group model.
+__host__ __device__ constexpr int x3_fast_quad(int tid) { return ((tid & 15) - (tid >> 4)) & 15; }
+
+// The store phase of an interior 192-channel x 128-pixel tile (x3_store_phase): bias, optional accumulate, range
+// tag and moments as the general loops below, value for value, without their per-item decode.  Thread tid owns
+// quads x3_fast_quad(tid) + 16 j (j < 3) of pixels (tid >> 4) + 32 k (k < 4): a wave's store covers 4 pixels x
+// 256 contiguous bytes.  TW divides 32, so the 4 pixels of a thread lie in one tile column, 32 / TW rows apart: one
+// 32-bit byte offset per thread and tile (voff), the rows as uniform bases, the quads as immediate offsets.
+// ACC: every load of the old output is issued before the first store, so the waits are counted and no store
+// waits for a load issued after the store before it (the general loop pays one load and one store round trip per
+// item).  The 12 quads fit the registers of the producer waves too, which hold the next tile's staged patch across
+// the phase (same-box A/B of 2, 3 or 4 pixels in flight there: no difference).
+template <bool ACC, bool ST>
+__device__ __forceinline__ void x3_store_fast(char* base, size_t kstride, unsigned voff, const float* tp,
+                                              const float* bp, float& amax, double& s1, double& s2) {
+    constexpr int TP = 192 + 4;
+    f32x4 bi[3], ov[4][3];
+#pragma unroll
+    for (int j = 0; j < 3; ++j) bi[j] = *reinterpret_cast<const f32x4*>(bp + 64 * j);
+    if constexpr (ACC) {
+#pragma unroll
+        for (int k = 0; k < 4; ++k)
+#pragma unroll
+            for (int j = 0; j < 3; ++j)
+                ov[k][j] = *reinterpret_cast<const f32x4*>(base + k * kstride + voff + 256 * j);
+    }
+    // one scheduling region per item, behind the pixel's 3 LDS reads: left free, the scheduler lifts the later
+    // items' moment terms over the earlier ones' serial fp64 adds and spills the producers' staged patch registers
+#pragma unroll
+    for (int k = 0; k < 4; ++k) {
+        __builtin_amdgcn_sched_barrier(0);
+        f32x4 tv[3];
+#pragma unroll
+        for (int j = 0; j < 3; ++j) tv[j] = *reinterpret_cast<const f32x4*>(tp + k * 32 * TP + 64 * j);
+#pragma unroll
+        for (int j = 0; j < 3; ++j) {
+            __builtin_amdgcn_sched_barrier(0);
+            const f32x4 acc = tv[j];
+            f32x4 r;
+#pragma unroll
+            for (int e = 0; e < 4; ++e) {
+                float v = acc[e] + bi[j][e];
+                if constexpr (ACC) v += ov[k][j][e];
+                r[e] = v;
+            }
+            amax = fmaxf(fmaxf(amax, fabsf(r[0])), fabsf(r[1]));
+            amax = fmaxf(fmaxf(amax, fabsf(r[2])), fabsf(r[3]));
+            *reinterpret_cast<f32x4*>(base + k * kstride + voff + 256 * j) = r;
+            if constexpr (ST) {  // the quad's fp32 partials as the general loops, one pair of fp64 adds per quad
+                // (written out in the roundings the compiler gives those loops — products rounded before the
+                // adds under accumulate, the fused chain r1 r1, + r0 r0, + r2 r2, + r3 r3 without — so that the
+                // fp32 partials of a quad, not only their fp64 sums, are the same on both paths)
+#pragma clang fp contract(off)
+                float f1 = 0.f, f2 = 0.f;
+                if constexpr (ACC) {
+#pragma unroll
+                    for (int e = 0; e < 4; ++e) {
+                        f1 += r[e] - ov[k][j][e];
+                        f2 += (r[e] - ov[k][j][e]) * (r[e] + ov[k][j][e]);
+                    }
+                } else {
+#pragma unroll
+                    for (int e = 0; e < 4; ++e) f1 += r[e];
+                    f2 = __builtin_fmaf(r[0], r[0], r[1] * r[1]);
+                    f2 = __builtin_fmaf(r[3], r[3], __builtin_fmaf(r[2], r[2], f2));
+                }
+                s1 += (double)f1;
+                s2 += (double)f2;
+                // (the sums are taken here: sunk to the end of the phase, the 12 items' converted partials
+                // stay live across it)
+                asm volatile("" : "+v"(s1), "+v"(s2));
+            }
+        }
+    }
+}
+
 // All 512 threads store the work-group's NCO-channel x TILE_PX tile from LDS (T[pixel][NCO + 4]):
 // NCO/4 consecutive threads cover one pixel's NCO channels (one contiguous run of the NHWC output), with
 // the fused bias / addends / GELU / accumulate of store_tile, in the same float order.
+// Wide tiles (NCO = 192) that lie wholly inside the output, with all 192 channels and the epilogue of the U-Net's
+// 3x3 / 2x2 convs (bias, optionally accumulate), take x3_store_fast instead (old_store: never — the test switch
+// of nps_launch_conv2d_x3).
 template <int TILE_PX, int NCO>
 __device__ __forceinline__ void x3_store_phase(const nps_conv2d_t& a, int b, int cob, int oy0, int ox0, int lat,
                                                int ph, const float* T, const float* btab, int tid, float& amax,
-                                               double* red) {
+                                               double* red, int old_store) {
     const int poy = a.out_off_y + (ph >> 1), pox = a.out_off_x + (ph & 1);  // transposed-conv phase offset
     constexpr int Q = NCO / 4;
     const bool st = a.out_stats != nullptr;
     double s1 = 0.0, s2 = 0.0;  // out_stats: fp64 sum / sum of squares of the stored values
+    if constexpr (NCO == 192) {
+        // one uniform test per tile: the tile's pixels and their destinations all exist, and every byte offset
+        // inside the tile's destination window fits 31 bits
+        const int dy0 = oy0 * a.out_os + poy, dx0 = ox0 * a.out_os + pox;
+        const bool fast = !old_store && lat == 1 && a.Cout == 192 && (a.out_C & 3) == 0 && a.act == 0 &&
+                          a.addend0 == nullptr && a.addend1 == nullptr && oy0 + a.TH <= a.Hout &&
+                          ox0 + a.TW <= a.Wout && dy0 >= 0 && dy0 + (a.TH - 1) * a.out_os < a.out_H && dx0 >= 0 &&
+                          dx0 + (a.TW - 1) * a.out_os < a.out_W &&
+                          (long long)a.TH * a.out_os * a.out_W * a.out_C < (1ll << 29);
+        if (fast) {
+            const int sh = 31 - __builtin_clz((unsigned)a.TW);  // TW is 4, 8, 16 or 32
+            const int p0 = tid >> 4, qr = x3_fast_quad(tid);
+            const int ti = p0 >> sh, tj = p0 & (a.TW - 1);
+            const unsigned voff = (unsigned)(((ti * a.out_W + tj) * a.out_os) * a.out_C + 4 * qr) * 4u;
+            const size_t kstride = (size_t)(32 >> sh) * a.out_os * a.out_W * a.out_C * 4;
+            char* base = reinterpret_cast<char*>(a.out + (((size_t)b * a.out_H + dy0) * a.out_W + dx0) * a.out_C);
+            const float* tp = T + p0 * (NCO + 4) + 4 * qr;
+            const float* bp = btab + 4 * qr;
+            if (a.accumulate)
+                st ? x3_store_fast<true, true>(base, kstride, voff, tp, bp, amax, s1, s2)
+                   : x3_store_fast<true, false>(base, kstride, voff, tp, bp, amax, s1, s2);
+            else
+                st ? x3_store_fast<false, true>(base, kstride, voff, tp, bp, amax, s1, s2)
+                   : x3_store_fast<false, false>(base, kstride, voff, tp, bp, amax, s1, s2);
+            stats_publish_wg<true>(a, b, s1, s2, red);
+            return;
+        }
+    }
     if (!a.accumulate && a.addend0 == nullptr && a.addend1 == nullptr) {
         // No operand to read: the bias comes from the LDS table and out-of-range items store to a sink, so the
         // loop holds no global load and no branch around a store.  (vmcnt retires loads and stores in one
@@ -108,7 +219,7 @@ __device__ __forceinline__ void x3_store_phase(const nps_conv2d_t& a, int b, int
                 s2 += ok ? (double)f2 : 0.0;
             }
         }
-        stats_publish_wg(a, b, s1, s2, red);
+        stats_publish_wg<true>(a, b, s1, s2, red);
         return;
     }
 #pragma unroll 4
@@ -150,7 +261,7 @@ __device__ __forceinline__ void x3_store_phase(const nps_conv2d_t& a, int b, int
             s2 += (double)f2;
         }
     }
-    stats_publish_wg(a, b, s1, s2, red);  // the next GroupNorm(1)'s moments of this sample: one pair per tile
+    stats_publish_wg<true>(a, b, s1, s2, red);  // the next GroupNorm(1)'s moments of this sample: one pair per tile
 }
 
 // PRO: the frame prologue (GroupNorm affine and/or GELU, proc_unet_modern.py:62-99) is applied by the
@@ -160,7 +271,7 @@ __device__ __forceinline__ void x3_store_phase(const nps_conv2d_t& a, int b, int
 // patch then feeds all 192 channels: 3x less producer work (fetch, split, prologue) and patch traffic per
 // MFMA than three 64-channel work-groups re-staging the same patch.
 template <int NTAPS, int PB, bool PRO, bool WIDE = false>
-__global__ __launch_bounds__(512) void conv2d_x3_kernel(const nps_conv2d_t a) {
+__global__ __launch_bounds__(512) void conv2d_x3_kernel(const nps_conv2d_t a, const int old_store) {
     constexpr int KWT = NTAPS == 25 ? 5 : (NTAPS == 9 ? 3 : (NTAPS == 4 ? 2 : 1));
     constexpr int CBW = WIDE ? 3 : 2;          // 32-channel co blocks per consumer wave
     constexpr int PBW = WIDE ? 2 : PB;         // 32-pixel blocks per consumer wave
@@ -406,7 +517,7 @@ __global__ __launch_bounds__(512) void conv2d_x3_kernel(const nps_conv2d_t a) {
             barrier();  // the consumers' tile is in LDS
             if (lds_epi)
                 x3_store_phase<TILE_PX, NCO>(a, sb, scob, soy0, sox0, g.T, sph, reinterpret_cast<const float*>(ring), btab, tid,
-                                             pmax, reinterpret_cast<double*>(smem));  // (red: the unused 128-B header)
+                                             pmax, reinterpret_cast<double*>(smem), old_store);  // (red: the unused 128-B header)
             barrier();  // every read of the staged tile is done: the ring may be refilled
             if (!more) break;
             l = ln;
@@ -547,7 +658,8 @@ __global__ __launch_bounds__(512) void conv2d_x3_kernel(const nps_conv2d_t a) {
                     }
             }
             barrier();
-            x3_store_phase<TILE_PX, NCO>(a, b, cob, oy0, ox0, g.T, ph, T, btab, tid, amax, reinterpret_cast<double*>(smem));
+            x3_store_phase<TILE_PX, NCO>(a, b, cob, oy0, ox0, g.T, ph, T, btab, tid, amax, reinterpret_cast<double*>(smem),
+                                         old_store);
         } else if constexpr (!WIDE) {
             static_for<PBW>([&](auto pbc) {  // compile-time pb: acc stays in registers
                 constexpr int pb = decltype(pbc)::value;
@@ -1007,6 +1119,12 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2))) void c
     }
 }
 
+// NPS_X3_STORE_OLD=1, read once per process
+int x3_old_store() {
+    static const int v = nps::env_flag("NPS_X3_STORE_OLD", false) ? 1 : 0;
+    return v;
+}
+
 template <int NT, int PB, bool PRO = false, bool WIDE = false>
 void launch_x3_one(const nps_conv2d_t& a, unsigned nwg, int lds, hipStream_t s) {
     static bool attr_set = false;
@@ -1015,7 +1133,9 @@ void launch_x3_one(const nps_conv2d_t& a, unsigned nwg, int lds, hipStream_t s) 
                                   hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
         attr_set = true;
     }
-    conv2d_x3_kernel<NT, PB, PRO, WIDE><<<nwg, 512, lds, s>>>(a);
+    // test-only switch (DESIGN.md § Retired run-time switches): NPS_X3_STORE_OLD=1 keeps every wide tile on the
+    // general store loops, so the fast store phase can be compared with them on the same pixels
+    conv2d_x3_kernel<NT, PB, PRO, WIDE><<<nwg, 512, lds, s>>>(a, x3_old_store());
 }
 
 
