@@ -6,6 +6,7 @@ to the reference; their forward never calls aten convolution: it runs the
 gfx950 implicit-GEMM kernel through nps_hip (fails loudly off-GPU).
 """
 import copy
+from typing import Callable, NamedTuple
 
 import torch
 from torch import nn
@@ -40,9 +41,9 @@ def activation_code(act):
     raise NotImplementedError(f"activation {act!r} is not fused on the MI355X path (GELU only)")
 
 
-def crop_offsets(cur_hw, des_hw):
-    """(top, left) placement of a cur-sized map inside a des-sized frame, crop_Nd semantics (common.py:20-34)."""
-    return ops.crop_offset(cur_hw[0], des_hw[0]), ops.crop_offset(cur_hw[1], des_hw[1])
+def crop_offsets(cur, des):
+    """Per-axis placement of a cur-sized map / volume inside a des-sized frame, crop_Nd semantics (common.py:20-34)."""
+    return tuple(ops.crop_offset(c, d) for c, d in zip(cur, des))
 
 
 def crop_Nd(num_spatial_dims, enc_ftrs, shape):
@@ -94,6 +95,12 @@ class Conv2d(_PackedMixin, nn.Conv2d):
             raise NotImplementedError(f"padding_mode {self.padding_mode}")
         return KH, KW, s, d, lo, hi, 0
 
+    def out_hw(self, H, W):
+        """Output size of this conv on an (H, W) frame."""
+        KH, KW, s, d, lo, hi, circ = self.geometry()
+        return ((H + 2 * circ + lo[0] + hi[0] - d * (KH - 1) - 1) // s + 1,
+                (W + 2 * circ + lo[1] + hi[1] - d * (KW - 1) - 1) // s + 1)
+
     def run(self, srcs, frame_hw, **kw):
         KH, KW, s, d, lo, hi, circ = self.geometry()
         x = srcs[0].t
@@ -103,8 +110,7 @@ class Conv2d(_PackedMixin, nn.Conv2d):
                 and "gn" not in kw and not kw.get("pre_act")):
             # U-Net Downsample: 3x3/s2 as a 2x2 stride-1 conv over the space-to-depth input
             p = lo[0]
-            Ho = (frame_hw[0] + 2 * p - 3) // 2 + 1
-            Wo = (frame_hw[1] + 2 * p - 3) // 2 + 1
+            Ho, Wo = self.out_hw(*frame_hw)
             pk2 = self._packed(ops.pack_conv_weight_s2d, "s2d")
             if ops.S2D_VIEW and x.shape[3] % 16 == 0 and pk2.nps_precision == ops.PREC_X3F16:
                 # the split-fp16 producers read the space-to-depth view straight from x (nps_conv2d_t.s2d)
@@ -172,11 +178,6 @@ class ConvTranspose2d_padded(ConvTranspose2d):
         self.pre_pad = pad
 
 
-def crop_offsets3(cur, des):
-    """(d, h, w) placement of a cur-sized volume inside a des-sized frame, crop_Nd semantics (common.py:20-34)."""
-    return tuple(ops.crop_offset(c, d) for c, d in zip(cur, des))
-
-
 def to_ndhwc(x):
     """(B, C, D, H, W) -> contiguous (B, D, H, W, C) on the HIP transpose (fp32; bf16 via fp32)."""
     B, C, D, H, W = x.shape
@@ -237,6 +238,11 @@ class Conv3d(_Packed3Mixin, _PackedMixin, nn.Conv3d):
             raise NotImplementedError(f"padding_mode {self.padding_mode}")
         return K, s, 0, p
 
+    def out_dhw(self, dhw):
+        """Output size of this conv on a (D, H, W) frame."""
+        K, s, circ, zpad = self.geometry3d()
+        return tuple((n + 2 * (circ + zpad) - K) // s + 1 for n in dhw)
+
     def run3d(self, srcs, frame_dhw, **kw):
         """srcs: ops.Src3 NDHWC sources (fp32 or bf16) of a virtual frame -> (B, Do, Ho, Wo, Cout)."""
         K, s, circ, zpad = self.geometry3d()
@@ -275,9 +281,7 @@ class Conv3d(_Packed3Mixin, _PackedMixin, nn.Conv3d):
 
     def forward(self, x):
         if tuple(self.kernel_size) != (1, 1, 1) or tuple(self.stride) != (1, 1, 1):
-            if use_autograd(self):
-                raise NotImplementedError("the 3-D U-Net is inference-only on the MI355X path (C5 rollout)")
-            return to_ncdhw(self.run3d([ops.Src3(to_ndhwc(x))], x.shape[2:]))
+            return run_form(self, x, None, lambda form, x, _: self.run3d([form.Src(x)], x.shape[1:4]))
         B, C, D, H, W = x.shape
         x4 = x.reshape(B, C, D * H, W)
         if use_autograd(self):
@@ -347,9 +351,7 @@ class ConvTranspose3d_padded(_Packed3Mixin, nn.ConvTranspose3d):
                           self.out_channels, 2, transposed=True, circ=self.pad, zpad=1, **kw)
 
     def forward(self, x):
-        if use_autograd(self):
-            raise NotImplementedError("the 3-D U-Net is inference-only on the MI355X path (C5 rollout)")
-        return to_ncdhw(self.run3d(to_ndhwc(x)))
+        return run_form(self, x, None, lambda form, x, _: self.run3d(x))
 
 
 def get_upconv_with_right_spatial_dim(spatial_dim, in_channels, out_channels, **kwargs):
@@ -370,3 +372,35 @@ def get_upconv_with_right_spatial_dim(spatial_dim, in_channels, out_channels, **
         del kw["padding_mode"]
         return ConvTranspose3d_padded((kw["kernel_size"] - 1) // 2, in_channels, out_channels, **kw)
     raise NotImplementedError(f"only 0<x<=2d convs implemented so far, but found spatial dim {spatial_dim}!")
+
+
+class Form(NamedTuple):
+    """One of the three ways the U-Net modules run on channels-last activations."""
+    run: str             # the per-module method: run / run_ad / run3d
+    Src: type            # ops.Src / ops.Src3
+    nd: int              # spatial dims: a map's size is shape[1:1 + nd]
+    upsample: Callable   # (Upsample.conv, h) -> the transposed conv's output
+    to_in: Callable      # channels-first -> channels-last at a module boundary
+    to_out: Callable     # and back
+
+
+def _upsample3d(conv, h):
+    st = ops.new_stats(h.shape[0], h) if ops.CARRY3D else None  # (moments of the 8 phases' outputs)
+    h = conv.run3d(h, out_stats=st)
+    return h if st is None else ops.attach_stats(h, st)
+
+
+INFER2D = Form("run", ops.Src, 2, lambda conv, h: conv.run(h), ops.nchw_to_nhwc, ops.nhwc_to_nchw)
+AUTOGRAD2D = Form("run_ad", ops.Src, 2, ad.conv_transpose2d, ad.to_nhwc, ad.to_nchw)
+INFER3D = Form("run3d", ops.Src3, 3, _upsample3d, to_ndhwc, to_ncdhw)
+
+
+def run_form(mod, x, vb, fn):
+    """The module boundary of a forward(): fn(form, x, vb) on the channels-last x and conditioning vb (or None) in
+    the form that x and the grad mode call for; the tensor or tuple of tensors it returns, channels-first."""
+    form = INFER3D if x.dim() == 5 else AUTOGRAD2D if use_autograd(mod) else INFER2D
+    if form is INFER3D and use_autograd(mod):
+        raise NotImplementedError("the 3-D U-Net is inference-only on the MI355X path (C5 rollout)")
+    vb = form.to_in(vb) if vb is not None else None
+    y = fn(form, form.to_in(x), vb)
+    return tuple(form.to_out(t) for t in y) if isinstance(y, tuple) else form.to_out(y)

@@ -9,6 +9,15 @@ chain of fused HIP launches on NHWC tensors:
     are sources of one virtual conv input frame with their crop offsets;
   * the final GN(8)+GELU+conv+crop is one conv launch whose epilogue can also
     fuse the U-FNO `GELU(h_fno + h_unet)` (proc_ufno.py:118).
+
+The model runs in three forms (models.common.Form): 2-D inference (`run`, the fused launches above), 2-D
+autograd (`run_ad`, the same kernels unfused plus their backward kernels) and 3-D inference (`run3d`, NDHWC).
+The down / middle / up traversal is written once, `UNetModern._walk(form, h, vb)`, and so is each
+Down / MiddleBlock body (`_run(form, x, vb)`); a form names the per-module method, the source tuple, the number
+of spatial dims and how an Upsample is applied.  What differs by algorithm stays written per form: the three
+ResidualBlock bodies, AttentionBlock, Downsample and the final conv stage of `UNetModern.run / run_ad / run3d`.
+Every forward() enters through models.common.run_form, which picks the form, converts the layout in and out and
+refuses 3-D under autograd.
 """
 from typing import List, Tuple, Union
 
@@ -17,7 +26,7 @@ from torch import nn
 
 from common.interfaces import D, M
 from models.common import (get_conv_with_right_spatial_dim, get_upconv_with_right_spatial_dim, crop_offsets,
-                           crop_offsets3, activation_code, use_autograd, to_ndhwc, to_ncdhw)
+                           activation_code, run_form, INFER2D, AUTOGRAD2D, INFER3D)
 from nps_hip import ops
 from nps_hip import autograd as ad
 from pdes import PDE
@@ -25,6 +34,21 @@ from pdes import PDE
 
 def _gn_args(norm_mod, stats):
     return ops.GN(stats, norm_mod.weight, norm_mod.bias, norm_mod.num_groups, float(norm_mod.eps))
+
+
+def _check_identity_input(srcs, size):
+    """An identity shortcut adds x itself: one source that is the whole frame."""
+    if len(srcs) != 1 or any(srcs[0][1:]) or tuple(srcs[0].t.shape[1:1 + len(size)]) != tuple(size):
+        raise RuntimeError("identity shortcut on a concatenated input")
+
+
+def _res_attn(form, m, res, srcs, size):
+    """m.attn(res(frame of srcs)) of a Down / Middle / Up block m in the given form."""
+    if isinstance(m.attn, nn.Identity):
+        return getattr(res, form.run)(srcs, size)
+    if form.nd == 3:
+        raise NotImplementedError("3-D U-Net attention is not on the MI355X path")
+    return getattr(m.attn, form.run)(getattr(res, form.run)(srcs, size))
 
 
 class UNetModern(nn.Module):
@@ -86,45 +110,51 @@ class UNetModern(nn.Module):
             self.final = get_conv_with_right_spatial_dim(num_spatial_dims, in_channels=hidden_features,
                                                          out_channels=hidden_features, kernel_size=3, **padding_kwargs)
 
-    def run(self, h, vb, addend=None, act_after=0, addend_fork=None):
-        """NHWC forward (proc_unet_modern.py:169-196).  Optional fused epilogue on the final conv:
-        out = act_after(final(...) + addend) — the U-FNO block combination.  addend_fork: the ops.Fork whose
-        side stream computes addend (joined just before the final conv)."""
-        if self.num_spatial_dims != 2:
-            raise NotImplementedError("UNetModern: 2-D only on the MI355X path")
+    def _walk(self, form, h, vb):
+        """Down, middle and up (proc_unet_modern.py:169-193) in the given form.  Returns the last feature map and the
+        input's shape (the final conv's crop target)."""
+        if self.num_spatial_dims != form.nd:
+            raise NotImplementedError("UNetModern: 2-D only on the MI355X path" if form.nd == 2 else
+                                      "UNetModern.run3d: 3-D U-Nets only")
         if self.n_cond > 0 and vb is None:
             # reference Downsample.forward returns a bare tensor here (proc_unet_modern.py:451-455) which
             # :175 then unpacks along the batch dimension; refuse instead of reproducing that bug
             raise ValueError("UNetModern with n_cond > 0 needs variables_broadcast")
         if self.n_cond == 0:
             vb = None
-        h_shape = h.shape
+        h_shape, sp = h.shape, slice(1, 1 + form.nd)
         feats, vbs = [h], [vb]
         for m in self.down:
             if isinstance(m, Downsample):
-                h, vb = m.run(h, vb)
+                h, vb = getattr(m, form.run)(h, vb)
             else:
-                h = m.run(h, vb)
+                h = m._run(form, h, vb)
             feats.append(h)
             vbs.append(vb)
-        h = self.middle.run(h, vb)
+        h = self.middle._run(form, h, vb)
         for m in self.up:
             if isinstance(m, Upsample):
-                h = m.conv.run(h)
+                h = form.upsample(m.conv, h)
             else:
-                s = feats.pop()
-                v = vbs.pop()
-                H, W = h.shape[1:3]
-                srcs = [ops.Src(h), ops.Src(s, *crop_offsets(s.shape[1:3], (H, W)))]
+                # cat((h, crop_Nd(skip), crop_Nd(vb))) as the three sources of one frame
+                s, v, size = feats.pop(), vbs.pop(), tuple(h.shape[sp])
+                srcs = [form.Src(h), form.Src(s, *crop_offsets(s.shape[sp], size))]
                 if v is not None:
-                    srcs.append(ops.Src(v, *crop_offsets(v.shape[1:3], (H, W))))
-                h = _attn(m, m.res.run(srcs, (H, W)))
+                    srcs.append(form.Src(v, *crop_offsets(v.shape[sp], size)))
+                h = _res_attn(form, m, m.res, srcs, size)
+        return h, h_shape
+
+    def run(self, h, vb, addend=None, act_after=0, addend_fork=None):
+        """NHWC forward (proc_unet_modern.py:169-196).  Optional fused epilogue on the final conv:
+        out = act_after(final(...) + addend) — the U-FNO block combination.  addend_fork: the ops.Fork whose
+        side stream computes addend (joined just before the final conv)."""
+        h, h_shape = self._walk(INFER2D, h, vb)
         # final: conv(act(norm(h))) then crop_Nd to the input size, as one launch
         H, W = h.shape[1:3]
         gn = None
         if isinstance(self.norm, nn.GroupNorm):
             gn = _gn_args(self.norm, ops.group_norm_stats([ops.Src(h)], (H, W), self.norm.num_groups))
-        oy, ox = crop_offsets(self.final_out_hw(H, W), h_shape[1:3])
+        oy, ox = crop_offsets(self.final.out_hw(H, W), h_shape[1:3])
         B, Ht, Wt = h_shape[0], h_shape[1], h_shape[2]
         if addend_fork is not None:
             addend_fork.join(addend)
@@ -140,80 +170,21 @@ class UNetModern(nn.Module):
 
     def run_ad(self, h, vb):
         """Differentiable NHWC forward (training): proc_unet_modern.py:169-196 as unfused HIP ops."""
-        if self.num_spatial_dims != 2:
-            raise NotImplementedError("UNetModern: 2-D only on the MI355X path")
-        if self.n_cond > 0 and vb is None:
-            raise ValueError("UNetModern with n_cond > 0 needs variables_broadcast")
-        if self.n_cond == 0:
-            vb = None
-        h_shape = h.shape
-        feats, vbs = [h], [vb]
-        for m in self.down:
-            if isinstance(m, Downsample):
-                h, vb = m.run_ad(h, vb)
-            else:
-                h = m.run_ad(h, vb)
-            feats.append(h)
-            vbs.append(vb)
-        h = self.middle.run_ad(h, vb)
-        for m in self.up:
-            if isinstance(m, Upsample):
-                h = ad.conv_transpose2d(m.conv, h)
-            else:
-                s = feats.pop()
-                v = vbs.pop()
-                H, W = h.shape[1:3]
-                srcs = [ops.Src(h), ops.Src(s, *crop_offsets(s.shape[1:3], (H, W)))]
-                if v is not None:
-                    srcs.append(ops.Src(v, *crop_offsets(v.shape[1:3], (H, W))))
-                h = _attn_ad(m, m.res.run_ad(srcs, (H, W)))
-        H, W = h.shape[1:3]
+        h, h_shape = self._walk(AUTOGRAD2D, h, vb)
         norm = self.norm if isinstance(self.norm, nn.GroupNorm) else None
-        y = ad.conv2d(self.final, ad.frame([ops.Src(h)], (H, W), norm, activation_code(self.activation)))
+        y = ad.conv2d(self.final, ad.frame([ops.Src(h)], h.shape[1:3], norm, activation_code(self.activation)))
         return ad.crop(y, h_shape[1:3], crop_offsets(y.shape[1:3], h_shape[1:3]))
 
     def run3d(self, h, vb, addend=None, act_after=0, addend_fork=None):
         """NDHWC forward of the 3-D U-Net (proc_unet_modern.py:169-196 with num_spatial_dims=3; the 3-D
         Upsample is this build's ConvTranspose3d_padded), fp32 or bf16 storage.  Optional fused epilogue on
         the final conv: out = act_after(final(...) + addend) — the U-FNO block combination."""
-        if self.num_spatial_dims != 3:
-            raise NotImplementedError("UNetModern.run3d: 3-D U-Nets only")
-        if self.n_cond > 0 and vb is None:
-            raise ValueError("UNetModern with n_cond > 0 needs variables_broadcast")
-        if self.n_cond == 0:
-            vb = None
-        h_shape = h.shape
-        feats, vbs = [h], [vb]
-        for m in self.down:
-            if isinstance(m, Downsample):
-                h, vb = m.run3d(h, vb)
-            else:
-                h = m.run3d(h, vb)
-            feats.append(h)
-            vbs.append(vb)
-        h = self.middle.run3d(h, vb)
-        for m in self.up:
-            if isinstance(m, Upsample):
-                st = ops.new_stats(h.shape[0], h) if ops.CARRY3D else None  # (moments of the 8 phases' outputs)
-                h = m.conv.run3d(h, out_stats=st)
-                if st is not None:
-                    ops.attach_stats(h, st)
-            else:
-                _check_no_attn(m)
-                s = feats.pop()
-                v = vbs.pop()
-                dhw = tuple(h.shape[1:4])
-                srcs = [ops.Src3(h), ops.Src3(s, *crop_offsets3(s.shape[1:4], dhw))]
-                if v is not None:
-                    srcs.append(ops.Src3(v, *crop_offsets3(v.shape[1:4], dhw)))
-                h = m.res.run3d(srcs, dhw)
+        h, h_shape = self._walk(INFER3D, h, vb)
         dhw = tuple(h.shape[1:4])
         gn = None
         if isinstance(self.norm, nn.GroupNorm):
             gn = _gn_args(self.norm, ops.gn_stats3d([ops.Src3(h)], dhw, self.norm.num_groups))
-        K, s, circ, zpad = self.final.geometry3d()
-        fo = tuple((n + 2 * (circ + zpad) - K) // s + 1 for n in dhw)
-        off = crop_offsets3(fo, h_shape[1:4])
+        off = crop_offsets(self.final.out_dhw(dhw), h_shape[1:4])
         if addend_fork is not None:
             addend_fork.join(addend)
         out = torch.empty(tuple(h_shape[:4]) + (self.final.out_channels,), dtype=h.dtype, device=h.device)
@@ -228,23 +199,9 @@ class UNetModern(nn.Module):
             ops.attach_stats(out, st)
         return out
 
-    def final_out_hw(self, H, W):
-        KH, KW, s, d, lo, hi, circ = self.final.geometry()
-        return ((H + 2 * circ + lo[0] + hi[0] - d * (KH - 1) - 1) // s + 1,
-                (W + 2 * circ + lo[1] + hi[1] - d * (KW - 1) - 1) // s + 1)
-
     def forward(self, h: torch.Tensor, variables_broadcast: torch.Tensor = None, pos=None):
         assert h.dim() == 2 + self.num_spatial_dims
-        if self.num_spatial_dims == 3:
-            if use_autograd(self):
-                raise NotImplementedError("the 3-D U-Net is inference-only on the MI355X path (C5 rollout)")
-            vb = to_ndhwc(variables_broadcast) if variables_broadcast is not None else None
-            return to_ncdhw(self.run3d(to_ndhwc(h), vb))
-        if use_autograd(self):
-            vb = ad.to_nhwc(variables_broadcast) if variables_broadcast is not None else None
-            return ad.to_nchw(self.run_ad(ad.to_nhwc(h), vb))
-        vb = ops.nchw_to_nhwc(variables_broadcast) if variables_broadcast is not None else None
-        return ops.nhwc_to_nchw(self.run(ops.nchw_to_nhwc(h), vb))
+        return run_form(self, h, variables_broadcast, lambda form, h, vb: getattr(self, form.run)(h, vb))
 
 
 class ResidualBlock(nn.Module):
@@ -279,10 +236,7 @@ class ResidualBlock(nn.Module):
         x0 = srcs[0].t
         if not (x0.is_cuda and ops.SIDE_STREAM):
             return None
-        KH, KW, s, d, lo, hi, circ = self.conv1.geometry()
-        Ho = (H + 2 * circ + lo[0] + hi[0] - d * (KH - 1) - 1) // s + 1
-        Wo = (W + 2 * circ + lo[1] + hi[1] - d * (KW - 1) - 1) // s + 1
-        idle = ops.last_round_idle(Ho, Wo, x0.shape[0], self.conv1.out_channels, x0.device,
+        idle = ops.last_round_idle(*self.conv1.out_hw(H, W), x0.shape[0], self.conv1.out_channels, x0.device,
                                    Cin=sum(s.t.shape[3] for s in srcs))
         return ops.Fork(x0, settle=[s.t for s in srcs]) if idle >= ops.SIDE_MIN_IDLE else None
 
@@ -299,8 +253,7 @@ class ResidualBlock(nn.Module):
         st2 = out = None
         fork = None
         if isinstance(self.shortcut, nn.Identity):
-            if len(srcs) != 1 or srcs[0].off_y or srcs[0].off_x or tuple(srcs[0].t.shape[1:3]) != (H, W):
-                raise RuntimeError("identity shortcut on a concatenated input")
+            _check_identity_input(srcs, frame_hw)
             out = ops.share_tag(srcs[0].t.clone(), srcs[0].t)  # conv2 accumulates into it: same bound
             if isinstance(self.norm1, nn.GroupNorm):
                 st2 = ops.copy_stats(ops.source_stats(srcs[0].t))
@@ -325,12 +278,8 @@ class ResidualBlock(nn.Module):
             gn2 = _gn_args(self.norm2, ops.group_norm_stats([ops.Src(h1)], (H1, W1), self.norm2.num_groups))
         if fork is not None:
             fork.join(out)  # conv2 accumulates into the shortcut output
-        KH, KW, s, d, lo, hi, circ = self.conv2.geometry()
-        H2 = (H1 + 2 * circ + lo[0] + hi[0] - d * (KH - 1) - 1) // s + 1
-        W2 = (W1 + 2 * circ + lo[1] + hi[1] - d * (KW - 1) - 1) // s + 1
-        oy, ox = crop_offsets((H2, W2), out.shape[1:3])
-        self.conv2.run([ops.Src(h1)], (H1, W1), gn=gn2, pre_act=act, out=out, out_off=(oy, ox), accumulate=True,
-                       out_stats=st2)
+        self.conv2.run([ops.Src(h1)], (H1, W1), gn=gn2, pre_act=act, out=out, accumulate=True, out_stats=st2,
+                       out_off=crop_offsets(self.conv2.out_hw(H1, W1), out.shape[1:3]))
         if st2 is not None:
             ops.attach_stats(out, st2)
         return out
@@ -354,12 +303,10 @@ class ResidualBlock(nn.Module):
         carry_out = ops.CARRY3D and isinstance(self.norm1, nn.GroupNorm)
         st_out = None
         if isinstance(self.shortcut, nn.Identity):
-            s0 = srcs[0]
-            if len(srcs) != 1 or s0.off_d or s0.off_h or s0.off_w or tuple(s0.t.shape[1:4]) != tuple(frame_dhw):
-                raise RuntimeError("identity shortcut on a concatenated input")
-            out = s0.t.clone()
+            _check_identity_input(srcs, frame_dhw)
+            out = srcs[0].t.clone()
             if carry_out:
-                st_out = ops.copy_stats(ops.source_stats3d(s0.t))
+                st_out = ops.copy_stats(ops.source_stats3d(srcs[0].t))
         else:
             st_out = ops.new_stats(B, srcs[0].t) if carry_out else None
             out = self.shortcut.run3d(srcs, frame_dhw, out_stats=st_out)
@@ -368,10 +315,8 @@ class ResidualBlock(nn.Module):
             st2 = (ops._stats_sum([st1], B, ops.new_stats(B, h1, 1)) if carry
                    else ops.gn_stats3d([ops.Src3(h1)], d1, self.norm2.num_groups))
             gn2 = _gn_args(self.norm2, st2)
-        K, s, circ, zpad = self.conv2.geometry3d()
-        d2 = tuple((n + 2 * (circ + zpad) - K) // s + 1 for n in d1)
-        self.conv2.run3d([ops.Src3(h1)], d1, gn=gn2, pre_act=act, out=out,
-                         out_off=crop_offsets3(d2, out.shape[1:4]), accumulate=True, out_stats=st_out)
+        self.conv2.run3d([ops.Src3(h1)], d1, gn=gn2, pre_act=act, out=out, accumulate=True, out_stats=st_out,
+                         out_off=crop_offsets(self.conv2.out_dhw(d1), out.shape[1:4]))
         if st_out is not None:
             ops.attach_stats(out, st_out)
         return out
@@ -383,8 +328,7 @@ class ResidualBlock(nn.Module):
         n1 = self.norm1 if isinstance(self.norm1, nn.GroupNorm) else None
         n2 = self.norm2 if isinstance(self.norm2, nn.GroupNorm) else None
         if isinstance(self.shortcut, nn.Identity):
-            if len(srcs) != 1 or srcs[0].off_y or srcs[0].off_x or tuple(srcs[0].t.shape[1:3]) != (H, W):
-                raise RuntimeError("identity shortcut on a concatenated input")
+            _check_identity_input(srcs, frame_hw)
         # conv1's frame and the shortcut's input (x itself for the identity) from one node: the backward adds the
         # shortcut path's gradient inside the frame backward (ad.frame_pair), not as a separate accumulation
         f1, xin = ad.frame_pair(srcs, (H, W), n1, act) if ad.FRAME_PAIR else (ad.frame(srcs, (H, W), n1, act), None)
@@ -397,16 +341,8 @@ class ResidualBlock(nn.Module):
         return ad.add_at(sc, h2, crop_offsets(h2.shape[1:3], sc.shape[1:3]))
 
     def forward(self, x: torch.Tensor):
-        if self.num_spatial_dims == 3:
-            if use_autograd(self):
-                raise NotImplementedError("the 3-D U-Net is inference-only on the MI355X path (C5 rollout)")
-            x = to_ndhwc(x)
-            return to_ncdhw(self.run3d([ops.Src3(x)], x.shape[1:4]))
-        if use_autograd(self):
-            x = ad.to_nhwc(x)
-            return ad.to_nchw(self.run_ad([ops.Src(x)], x.shape[1:3]))
-        x = ops.nchw_to_nhwc(x)
-        return ops.nhwc_to_nchw(self.run([ops.Src(x)], x.shape[1:3]))
+        return run_form(self, x, None, lambda form, x, _: getattr(self, form.run)(
+            [form.Src(x)], x.shape[1:1 + form.nd]))
 
 
 _GEO_1X1 = (1, 1, 1, 1, (0, 0), (0, 0), 0)  # Conv2d.geometry() of a 1x1 conv
@@ -488,22 +424,12 @@ class AttentionBlock(nn.Module):
     def forward(self, x: torch.Tensor):
         if x.dim() != 4:
             raise NotImplementedError("U-Net attention: 2-D maps only on the MI355X path")
-        if use_autograd(self):
-            return ad.to_nchw(self.run_ad(ad.to_nhwc(x)))
-        return ops.nhwc_to_nchw(self.run(ops.nchw_to_nhwc(x)))
+        return run_form(self, x, None, lambda form, x, _: getattr(self, form.run)(x))
 
 
-def _check_no_attn(m):
-    if not isinstance(m.attn, nn.Identity):
-        raise NotImplementedError("3-D U-Net attention is not on the MI355X path")
-
-
-def _attn(m, h):
-    return h if isinstance(m.attn, nn.Identity) else m.attn.run(h)
-
-
-def _attn_ad(m, h):
-    return h if isinstance(m.attn, nn.Identity) else m.attn.run_ad(h)
+def _frame(form, x, vb):
+    """cat((x, vb)) as the sources of one frame."""
+    return [form.Src(x)] + ([form.Src(vb)] if vb is not None else [])
 
 
 class DownBlock(nn.Module):
@@ -516,28 +442,11 @@ class DownBlock(nn.Module):
                                  num_spatial_dims=num_spatial_dims, padding_kwargs=padding_kwargs)
         self.attn = AttentionBlock(out_channels, num_spatial_dims=num_spatial_dims) if has_attn else nn.Identity()
 
-    def run(self, x, vb):
-        srcs = [ops.Src(x)] + ([ops.Src(vb)] if vb is not None else [])
-        return _attn(self, self.res.run(srcs, x.shape[1:3]))
-
-    def run_ad(self, x, vb):
-        srcs = [ops.Src(x)] + ([ops.Src(vb)] if vb is not None else [])
-        return _attn_ad(self, self.res.run_ad(srcs, x.shape[1:3]))
-
-    def run3d(self, x, vb):
-        _check_no_attn(self)
-        srcs = [ops.Src3(x)] + ([ops.Src3(vb)] if vb is not None else [])
-        return self.res.run3d(srcs, x.shape[1:4])
+    def _run(self, form, x, vb):
+        return _res_attn(form, self, self.res, _frame(form, x, vb), x.shape[1:1 + form.nd])
 
     def forward(self, x: torch.Tensor, variables_broadcast: torch.Tensor = None):
-        if self.res.num_spatial_dims == 3:
-            vb = to_ndhwc(variables_broadcast) if variables_broadcast is not None else None
-            return to_ncdhw(self.run3d(to_ndhwc(x), vb)), variables_broadcast
-        if use_autograd(self):
-            vb = ad.to_nhwc(variables_broadcast) if variables_broadcast is not None else None
-            return ad.to_nchw(self.run_ad(ad.to_nhwc(x), vb)), variables_broadcast
-        vb = ops.nchw_to_nhwc(variables_broadcast) if variables_broadcast is not None else None
-        return ops.nhwc_to_nchw(self.run(ops.nchw_to_nhwc(x), vb)), variables_broadcast
+        return run_form(self, x, variables_broadcast, self._run), variables_broadcast
 
 
 class UpBlock(nn.Module):
@@ -551,14 +460,8 @@ class UpBlock(nn.Module):
         self.attn = AttentionBlock(out_channels, num_spatial_dims=num_spatial_dims) if has_attn else nn.Identity()
 
     def forward(self, x: torch.Tensor):
-        if self.res.num_spatial_dims == 3:
-            _check_no_attn(self)
-            return self.res(x)
-        if use_autograd(self):
-            x = ad.to_nhwc(x)
-            return ad.to_nchw(_attn_ad(self, self.res.run_ad([ops.Src(x)], x.shape[1:3])))
-        x = ops.nchw_to_nhwc(x)
-        return ops.nhwc_to_nchw(_attn(self, self.res.run([ops.Src(x)], x.shape[1:3])))
+        return run_form(self, x, None, lambda form, x, _: _res_attn(
+            form, self, self.res, [form.Src(x)], x.shape[1:1 + form.nd]))
 
 
 class MiddleBlock(nn.Module):
@@ -573,31 +476,12 @@ class MiddleBlock(nn.Module):
         self.res2 = ResidualBlock(out_channels, out_channels, activation=activation, norm=norm,
                                   num_spatial_dims=num_spatial_dims, padding_kwargs=padding_kwargs)
 
-    def run(self, x, vb):
-        srcs = [ops.Src(x)] + ([ops.Src(vb)] if vb is not None else [])
-        h = _attn(self, self.res1.run(srcs, x.shape[1:3]))
-        return self.res2.run([ops.Src(h)], h.shape[1:3])
-
-    def run_ad(self, x, vb):
-        srcs = [ops.Src(x)] + ([ops.Src(vb)] if vb is not None else [])
-        h = _attn_ad(self, self.res1.run_ad(srcs, x.shape[1:3]))
-        return self.res2.run_ad([ops.Src(h)], h.shape[1:3])
-
-    def run3d(self, x, vb):
-        _check_no_attn(self)
-        srcs = [ops.Src3(x)] + ([ops.Src3(vb)] if vb is not None else [])
-        h = self.res1.run3d(srcs, x.shape[1:4])
-        return self.res2.run3d([ops.Src3(h)], h.shape[1:4])
+    def _run(self, form, x, vb):
+        h = _res_attn(form, self, self.res1, _frame(form, x, vb), x.shape[1:1 + form.nd])
+        return getattr(self.res2, form.run)([form.Src(h)], h.shape[1:1 + form.nd])
 
     def forward(self, x: torch.Tensor, variables_broadcast: torch.Tensor = None):
-        if self.res1.num_spatial_dims == 3:
-            vb = to_ndhwc(variables_broadcast) if variables_broadcast is not None else None
-            return to_ncdhw(self.run3d(to_ndhwc(x), vb)), variables_broadcast
-        if use_autograd(self):
-            vb = ad.to_nhwc(variables_broadcast) if variables_broadcast is not None else None
-            return ad.to_nchw(self.run_ad(ad.to_nhwc(x), vb)), variables_broadcast
-        vb = ops.nchw_to_nhwc(variables_broadcast) if variables_broadcast is not None else None
-        return ops.nhwc_to_nchw(self.run(ops.nchw_to_nhwc(x), vb)), variables_broadcast
+        return run_form(self, x, variables_broadcast, self._run), variables_broadcast
 
 
 class Upsample(nn.Module):
@@ -647,15 +531,6 @@ class Downsample(nn.Module):
         return h, vb
 
     def forward(self, x: torch.Tensor, variables_broadcast: torch.Tensor = None):
-        if use_autograd(self):
-            if variables_broadcast is not None:
-                h, v = self.run_ad(ad.to_nhwc(x), ad.to_nhwc(variables_broadcast))
-                return ad.to_nchw(h), ad.to_nchw(v)
+        if variables_broadcast is None:
             return self.conv(x)
-        if variables_broadcast is not None and x.dim() == 5:
-            h, v = self.run3d(to_ndhwc(x), to_ndhwc(variables_broadcast))
-            return to_ncdhw(h), to_ncdhw(v)
-        if variables_broadcast is not None:
-            h, v = self.run(ops.nchw_to_nhwc(x), ops.nchw_to_nhwc(variables_broadcast))
-            return ops.nhwc_to_nchw(h), ops.nhwc_to_nchw(v)
-        return self.conv(x)
+        return run_form(self, x, variables_broadcast, lambda form, x, vb: getattr(self, form.run)(x, vb))

@@ -566,6 +566,14 @@ class GN(NamedTuple):
     eps: float
 
 
+def _set_prologue(a, gn: Optional[GN], pre_act):
+    """The GroupNorm + activation prologue fields of a Conv2dArgs / Conv3dArgs."""
+    if gn is not None:
+        a.gn_stats, a.gn_gamma, a.gn_beta = ptr(gn.stats), ptr(gn.gamma), ptr(gn.beta)
+        a.gn_groups, a.gn_eps = gn.groups, gn.eps
+    a.pre_act = pre_act
+
+
 def group_norm_stats(srcs: Sequence[Src], frame_hw, groups: int) -> torch.Tensor:
     """(B, groups, 2) fp64 (sum, sum of squares) of the virtual frame's groups — the moments of
     nn.GroupNorm.  GroupNorm(1) of sources that each lie wholly inside the frame (crop_Nd zero-pads them,
@@ -648,10 +656,7 @@ def conv2d(srcs: Sequence[Src], frame_hw, wpack: torch.Tensor, bias: Optional[to
     a.B, a.Hin, a.Win, a.Cin = B, Hin, Win, Cin
     if s2d_pad is not None:
         a.s2d, a.s2d_pad = 1, int(s2d_pad)
-    if gn is not None:
-        a.gn_stats, a.gn_gamma, a.gn_beta = ptr(gn.stats), ptr(gn.gamma), ptr(gn.beta)
-        a.gn_groups, a.gn_eps = gn.groups, gn.eps
-    a.pre_act = pre_act
+    _set_prologue(a, gn, pre_act)
     a.KH, a.KW, a.stride, a.dil = KH, KW, stride, dil
     a.pad_y, a.pad_x, a.circ = pad[0], pad[1], circ
     a.Hout, a.Wout = Hout, Wout
@@ -746,10 +751,7 @@ def frame_pack(srcs: Sequence[Src], frame_hw, gn: Optional[GN] = None, pre_act=0
     a.nsrc = len(srcs)
     a.src = _c_src(srcs)
     a.B, a.Hin, a.Win, a.Cin = B, Hin, Win, Cin
-    if gn is not None:
-        a.gn_stats, a.gn_gamma, a.gn_beta = ptr(gn.stats), ptr(gn.gamma), ptr(gn.beta)
-        a.gn_groups, a.gn_eps = gn.groups, gn.eps
-    a.pre_act = pre_act
+    _set_prologue(a, gn, pre_act)
     a.out_C = (Cin + 3) // 4 * 4 if pad4 else Cin
     out = empty_nhwc(B, Hin, Win, a.out_C, t0)
     a.out_tag = new_tag(out)
@@ -1310,10 +1312,7 @@ CONV3D_PACK = os.environ.get("NPS_CONV3D_PACK", "1") == "1"
 def frame_pack3d(srcs: Sequence[Src3], frame_dhw, gn: Optional[GN] = None, pre_act=0) -> torch.Tensor:
     """(B, Dc, Hc, Wc, Cpad) = act(GN(virtual frame)), channels zero-padded to a multiple of 16."""
     a = _fill_frame3(Conv3dArgs(), srcs, frame_dhw)
-    if gn is not None:
-        a.gn_stats, a.gn_gamma, a.gn_beta = ptr(gn.stats), ptr(gn.gamma), ptr(gn.beta)
-        a.gn_groups, a.gn_eps = gn.groups, gn.eps
-    a.pre_act = pre_act
+    _set_prologue(a, gn, pre_act)
     cpad = (a.Cin + 15) // 16 * 16
     out = torch.empty((a.B, a.Dc, a.Hc, a.Wc, cpad), dtype=srcs[0].t.dtype, device=srcs[0].t.device)
     check(lib.nps_frame_pack3d(ctypes_byref(a), ptr(out), cpad, stream_ptr()), "frame_pack3d")
@@ -1351,10 +1350,7 @@ def conv3d(srcs: Sequence[Src3], frame_dhw, wpack: torch.Tensor, bias: Optional[
     if addend is not None and (addend.shape != out.shape or addend.dtype != dt or not addend.is_contiguous()):
         raise RuntimeError("nps_hip conv3d: addend must be laid out like out")
     a.circ, a.zpad = circ, zpad
-    if gn is not None:
-        a.gn_stats, a.gn_gamma, a.gn_beta = ptr(gn.stats), ptr(gn.gamma), ptr(gn.beta)
-        a.gn_groups, a.gn_eps = gn.groups, gn.eps
-    a.pre_act = pre_act
+    _set_prologue(a, gn, pre_act)
     a.K, a.stride, a.transposed = K, stride, 1 if transposed else 0
     a.Dout, a.Hout, a.Wout = Dout, Hout, Wout
     a.out_stats = ptr(out_stats)  # (new_stats(B, ..) buffer: the stored values' GroupNorm(1) moments)
