@@ -669,6 +669,35 @@ int nps_frame_pack3d(const nps_conv3d_t* a, void* out, int Cpad, void* stream);
  * fp64 (sum, sum of squares) of the frame's values (uncovered positions count as 0) to stats[B][G][2] */
 int nps_gn_stats3d(const nps_conv3d_t* a, int G, double* stats, void* stream);
 
+/* ---- 3-D conv backward (fp32 training of Conv3d and the 3-D Upsample) ----
+ * Input gradients are nps_conv3d_fwd launches on dy with weights derived from the parameter (nps_hip/autograd.py
+ * Conv3dFn / ConvTranspose3dFn); the entries below provide the rest.
+ *
+ * Weight gradient on exact fp32 MFMA (v_mfma_f32_32x32x2_f32, fp32 accumulate):
+ *   g[m][n][(kd*K + kh)*K + kw] += sum_{b,pd,ph,pw} a[b][pd][ph][pw][m] * Xext[b][pd*S + kd][ph*S + kh][pw*S + kw][n]
+ * Xext = x extended per side of every axis by `circ` voxels circularly, then `zpad` zeros (nps_conv3d_t.circ /
+ * .zpad); a's extent must be the valid K^3 / stride-S conv's output over Xext.  With a = dy and x = the conv's
+ * input, g is nn.Conv3d.weight.grad [Cout][Cin][K][K][K]; with K = 4, S = 2, a = the (circularly padded) input of a
+ * k4/s2 transposed conv and x = dy, g is nn.ConvTranspose3d.weight.grad [Cin][Cout][4][4][4]. */
+typedef struct {
+    const float* a; int B, Da, Ha, Wa, M;     /* [B][Da][Ha][Wa][M] */
+    const float* x; int Dx, Hx, Wx, N;        /* [B][Dx][Hx][Wx][N] */
+    int K, stride, circ, zpad;                /* K in {1,2,3,4}, stride in {1,2} */
+    float* g;                                 /* [M][N][K*K*K], accumulated with += */
+} nps_wgrad3d_t;
+int nps_conv3d_wgrad(const nps_wgrad3d_t* p, void* stream);
+/* Host only: the number of work-groups that share one (m tile, n tile, tap group)'s voxel reduction in that launch
+ * (each adds its partial into g atomically), or < 0 where nps_conv3d_wgrad would refuse p. */
+int nps_conv3d_wgrad_splits(const nps_wgrad3d_t* p);
+/* out[B][Dq][Hq][Wq][8 C], channel ((rd*2 + rh)*2 + rw)*C + c = x[b][2 dq + rd][2 hq + rh][2 wq + rw][c] (0 outside
+ * x [B][D][H][W][C]): a K = 4 / stride-2 conv of x is a K = 2 / stride-1 conv of out */
+int nps_space_to_depth3d(const float* x, float* out, int B, int D, int H, int W, int C, int Dq, int Hq, int Wq,
+                         void* stream);
+/* circular pad by `pad` voxels per side of every axis of x [B][D][H][W][C] (out [B][D+2p][H+2p][W+2p][C]), and its
+ * adjoint: gx = the wrap-sum of gp [B][D+2p][H+2p][W+2p][C] */
+int nps_circular_pad3d(const float* x, float* out, int B, int D, int H, int W, int C, int pad, void* stream);
+int nps_circular_fold3d(const float* gp, float* gx, int B, int D, int H, int W, int C, int pad, void* stream);
+
 /* ---- U-Net self-attention (proc_unet_modern.py:292-317), never materialising the N x N scores ----
  * Layouts, exactly as the qkv projection writes them (no q / k / v split copies):
  *   qkv, dqkv [B][N][heads][3*dk]  (per head [q | k | v], dk floats each)

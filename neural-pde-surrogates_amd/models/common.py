@@ -196,6 +196,15 @@ def to_ncdhw(y):
     return (ops.to_bf16(x) if bf else x).view(B, C, D, H, W)
 
 
+def _ad_ncdhw(fn, conv, x):
+    """fn(conv, x) — ad.conv3d / ad.conv_transpose3d, on NDHWC — around the differentiable layout transposes of an
+    fp32 (B, C, D, H, W) tensor: NCDHW <-> NDHWC is the NCHW <-> NHWC permutation of the (B, C, D*H, W) view."""
+    B, C, D, H, W = x.shape
+    y = fn(conv, ad.to_nhwc(x.reshape(B, C, D * H, W)).view(B, D, H, W, C))
+    _, Do, Ho, Wo, Co = y.shape
+    return ad.to_nchw(y.view(B, Do * Ho, Wo, Co)).view(B, Co, Do, Ho, Wo)
+
+
 class _Packed3Mixin:
     """Caches the nps_conv3d packing of `weight` per storage dtype, re-packed when the parameter changes."""
 
@@ -281,6 +290,8 @@ class Conv3d(_Packed3Mixin, _PackedMixin, nn.Conv3d):
 
     def forward(self, x):
         if tuple(self.kernel_size) != (1, 1, 1) or tuple(self.stride) != (1, 1, 1):
+            if use_autograd(self) and x.dtype == torch.float32:
+                return _ad_ncdhw(ad.conv3d, self, x)
             return run_form(self, x, None, lambda form, x, _: self.run3d([form.Src(x)], x.shape[1:4]))
         B, C, D, H, W = x.shape
         x4 = x.reshape(B, C, D * H, W)
@@ -351,6 +362,8 @@ class ConvTranspose3d_padded(_Packed3Mixin, nn.ConvTranspose3d):
                           self.out_channels, 2, transposed=True, circ=self.pad, zpad=1, **kw)
 
     def forward(self, x):
+        if use_autograd(self) and x.dtype == torch.float32:
+            return _ad_ncdhw(ad.conv_transpose3d, self, x)
         return run_form(self, x, None, lambda form, x, _: self.run3d(x))
 
 

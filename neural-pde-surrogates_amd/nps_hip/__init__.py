@@ -13,7 +13,7 @@ import os
 
 import torch
 
-__all__ = ["lib", "Src", "Conv2dArgs", "WgradArgs", "Src3", "Conv3dArgs", "PackJob", "check", "stream_ptr", "ptr", "LIB_PATH"]
+__all__ = ["lib", "Src", "Conv2dArgs", "WgradArgs", "Wgrad3dArgs", "Src3", "Conv3dArgs", "PackJob", "check", "stream_ptr", "ptr", "LIB_PATH"]
 
 LIB_PATH = os.environ.get("NPS_HIP_LIB", os.path.join(os.path.dirname(os.path.abspath(__file__)), "libnps_hip.so"))
 if not os.path.exists(LIB_PATH):
@@ -86,6 +86,16 @@ class Conv3dArgs(ctypes.Structure):
         ("out_W", ctypes.c_int), ("out_os", ctypes.c_int), ("out_off_d", ctypes.c_int), ("out_off_h", ctypes.c_int),
         ("out_off_w", ctypes.c_int), ("accumulate", ctypes.c_int), ("addend", ctypes.c_void_p), ("act", ctypes.c_int),
         ("bf16", ctypes.c_int), ("out_stats", ctypes.c_void_p),
+    ]
+
+
+class Wgrad3dArgs(ctypes.Structure):
+    _fields_ = [
+        ("a", ctypes.c_void_p), ("B", ctypes.c_int), ("Da", ctypes.c_int), ("Ha", ctypes.c_int), ("Wa", ctypes.c_int),
+        ("M", ctypes.c_int),
+        ("x", ctypes.c_void_p), ("Dx", ctypes.c_int), ("Hx", ctypes.c_int), ("Wx", ctypes.c_int), ("N", ctypes.c_int),
+        ("K", ctypes.c_int), ("stride", ctypes.c_int), ("circ", ctypes.c_int), ("zpad", ctypes.c_int),
+        ("g", ctypes.c_void_p),
     ]
 
 
@@ -212,6 +222,12 @@ _SIGS = {
     "nps_conv3d_fwd": (_i, [ctypes.POINTER(Conv3dArgs), _vp]),
     "nps_gn_stats3d": (_i, [ctypes.POINTER(Conv3dArgs), _i, _vp, _vp]),
     "nps_frame_pack3d": (_i, [ctypes.POINTER(Conv3dArgs), _vp, _i, _vp]),
+    # 3-D conv backward
+    "nps_conv3d_wgrad": (_i, [ctypes.POINTER(Wgrad3dArgs), _vp]),
+    "nps_conv3d_wgrad_splits": (_i, [ctypes.POINTER(Wgrad3dArgs)]),
+    "nps_space_to_depth3d": (_i, [_vp, _vp, _i, _i, _i, _i, _i, _i, _i, _i, _vp]),
+    "nps_circular_pad3d": (_i, [_vp, _vp, _i, _i, _i, _i, _i, _i, _vp]),
+    "nps_circular_fold3d": (_i, [_vp, _vp, _i, _i, _i, _i, _i, _i, _vp]),
     # U-Net self-attention (column softmax), flash-style
     "nps_attn_colstats": (_i, [_vp, _vp, _i, _i, _i, _i, ctypes.c_float, _vp]),
     "nps_attn_fwd": (_i, [_vp, _vp, _vp, _i, _i, _i, _i, ctypes.c_float, _vp]),

@@ -486,6 +486,137 @@ def conv_transpose2d(conv, x: torch.Tensor) -> torch.Tensor:
     return ConvTranspose2dFn.apply((conv.pre_pad, conv.padding[0]), x, conv.weight, conv.bias)
 
 
+# ------------------------------------------------------------------------- 3-D conv
+def _check_geo3(geo):
+    """The 3-D conv geometries that have a backward: K^3 in 1..3 at stride 1 — valid / zero-padded by at most K - 1,
+    or circular 'same' — and the K = 3 stride-2 Downsample with zero padding 0 or 1."""
+    K, s, circ, zpad = geo
+    ok = 1 <= K <= 3 and circ >= 0 and zpad >= 0 and not (circ and zpad)
+    if s == 1:
+        ok = ok and zpad <= K - 1 and (circ == 0 or 2 * circ == K - 1)
+    elif s == 2:
+        if ok and circ:
+            raise NotImplementedError("3-D stride-2 conv with circular padding has no backward on the MI355X path")
+        ok = ok and K == 3 and zpad in (0, 1)
+    else:
+        ok = False
+    if not ok:
+        raise NotImplementedError(f"3-D conv backward: K={K} stride={s} circ={circ} zpad={zpad} is not supported")
+
+
+def _fp32_3d(x, weight, what):
+    if x.dtype != torch.float32 or weight.dtype != torch.float32:
+        raise NotImplementedError(f"{what}: the 3-D convs differentiate fp32 tensors only (use fp32 for training)")
+    if x.dim() != 5:
+        raise RuntimeError(f"{what}: NDHWC input expected, got {tuple(x.shape)}")
+
+
+def _pack3(w, transposed=False):
+    return ops.pack_conv3d_weight(w, transposed=transposed)
+
+
+class Conv3dFn(torch.autograd.Function):
+    """nn.Conv3d forward/backward on NDHWC fp32 (models/common.py Conv3d.run3d): geo = Conv3d.geometry3d() =
+    (K, stride, circ, zpad).  Input gradient = nps_conv3d_fwd launches on dy — stride 1: the conv with flipped,
+    channel-swapped weights over dy extended by K - 1 - zpad zeros (circularly for circular 'same'); stride 2: one
+    transposed-mode launch (8 K = 2 phases) with the k3 weight zero-padded to k4, shifted by -zpad and cropped to x,
+    which stores every voxel of dx (those no output reads get exact zeros).  Weight gradient = nps_conv3d_wgrad."""
+
+    @staticmethod
+    def forward(ctx, geo, x, weight, bias):
+        _check_geo3(geo)
+        _fp32_3d(x, weight, "Conv3dFn")
+        K, s, circ, zpad = geo
+        x = _c(x)
+        y = ops.conv3d([ops.Src3(x)], x.shape[1:4], ops.cached_pack(weight, "conv3", _pack3), bias, weight.shape[0], K,
+                       stride=s, circ=circ, zpad=zpad)
+        ctx.geo, ctx.has_bias = geo, bias is not None
+        ctx.param = weight  # the nn.Parameter itself: its input-gradient packing is cached on it (ops.cached_pack)
+        ctx.save_for_backward(x, weight)
+        return y
+
+    @staticmethod
+    def backward(ctx, gy):
+        K, s, circ, zpad = ctx.geo
+        x, w = ctx.saved_tensors
+        gy = _c(gy)
+        B, D, H, W, Cin = x.shape
+        dx = dw = db = None
+        fork = ops.Fork(gy, on=ops.SIDE_WGRAD and ctx.needs_input_grad[1] and ctx.needs_input_grad[2])
+        if ctx.needs_input_grad[1]:
+            if s == 1:
+                wd = ops.cached_pack(ctx.param, "dgrad3", lambda p: _pack3(ops.conv3d_dgrad_weight(p)))
+                dx = ops.conv3d([ops.Src3(gy)], gy.shape[1:4], wd, None, Cin, K, circ=circ,
+                                zpad=0 if circ else K - 1 - zpad)
+            else:
+                wt = ops.cached_pack(ctx.param, "dgrad3_s2",
+                                     lambda p: _pack3(ops.conv3d_s2_dgrad_weight(p), transposed=True))
+                dx = torch.empty_like(x)
+                ops.conv3d([ops.Src3(gy)], gy.shape[1:4], wt, None, Cin, 2, transposed=True, zpad=1, out=dx, out_os=2,
+                           out_off=(-zpad,) * 3)
+        if ctx.needs_input_grad[2]:
+            with fork:  # beside the input-gradient conv, as in Conv2dFn.backward
+                dw = ops.conv3d_wgrad(gy, x, K, stride=s, circ=circ, zpad=zpad)
+            fork.join(dw)
+        if ctx.has_bias and ctx.needs_input_grad[3]:
+            db = channel_sums(gy)
+        return None, dx, dw, db
+
+
+class ConvTranspose3dFn(torch.autograd.Function):
+    """The 3-D U-Net Upsample on NDHWC fp32 (models/common.py ConvTranspose3d_padded): circular pad geo = (pad,),
+    then nn.ConvTranspose3d(k=4, s=2, p=0).  The adjoint is the K = 4 / stride-2 conv of dy — a K = 2 conv over dy's
+    space-to-depth form (8 Cout channels) — followed by the fold of the circular border onto the core; the weight
+    gradient is the K = 4 / stride-2 nps_conv3d_wgrad with the roles swapped (a = the padded input, x = dy)."""
+
+    @staticmethod
+    def forward(ctx, geo, x, weight, bias):
+        _fp32_3d(x, weight, "ConvTranspose3dFn")
+        (c,) = geo
+        x = _c(x)
+        out = ops.conv3d([ops.Src3(x)], x.shape[1:4], ops.cached_pack(weight, "convT3", lambda p: _pack3(p, True)),
+                         bias, weight.shape[1], 2, transposed=True, circ=c, zpad=1)
+        ctx.geo, ctx.has_bias = geo, bias is not None
+        ctx.param = weight
+        ctx.save_for_backward(x, weight)
+        return out
+
+    @staticmethod
+    def backward(ctx, gout):
+        (c,) = ctx.geo
+        x, w = ctx.saved_tensors
+        gout = _c(gout)
+        B, D, H, W, Cin = x.shape
+        Dp, Hp, Wp = D + 2 * c, H + 2 * c, W + 2 * c
+        dx = dw = db = None
+        fork = ops.Fork(gout, on=ops.SIDE_WGRAD and ctx.needs_input_grad[1] and ctx.needs_input_grad[2])
+        if ctx.needs_input_grad[1]:
+            dq = ops.space_to_depth3d(gout, Dp + 1, Hp + 1, Wp + 1)           # [B][Dp+1][Hp+1][Wp+1][8 Cout]
+            wd = ops.cached_pack(ctx.param, "dgradT3", lambda p: _pack3(ops.conv_transpose3d_dgrad_weight(p)))
+            dxp = ops.conv3d([ops.Src3(dq)], dq.shape[1:4], wd, None, Cin, 2)
+            dx = ops.circular_fold3d(dxp, c) if c else dxp
+        if ctx.needs_input_grad[2]:
+            with fork:
+                dw = ops.conv3d_wgrad(ops.circular_pad3d(x, c) if c else x, gout, 4, stride=2)
+            fork.join(dw)
+        if ctx.has_bias and ctx.needs_input_grad[3]:
+            db = channel_sums(gout)
+        return None, dx, dw, db
+
+
+def conv3d(conv, x: torch.Tensor) -> torch.Tensor:
+    """Differentiable forward of a models.common.Conv3d on an NDHWC fp32 tensor."""
+    return Conv3dFn.apply(conv.geometry3d(), x, conv.weight, conv.bias)
+
+
+def conv_transpose3d(conv, x: torch.Tensor) -> torch.Tensor:
+    """Differentiable forward of a models.common.ConvTranspose3d_padded on an NDHWC fp32 tensor."""
+    if (set(conv.kernel_size) != {4} or set(conv.stride) != {2} or set(conv.padding) != {0}
+            or set(conv.output_padding) != {0} or set(conv.dilation) != {1} or conv.groups != 1):
+        raise NotImplementedError("3-D Upsample: ConvTranspose3d(k=4, s=2, p=0) only")
+    return ConvTranspose3dFn.apply((conv.pad,), x, conv.weight, conv.bias)
+
+
 # ------------------------------------------------------------------------- element-wise
 class GeluFn(torch.autograd.Function):
     """nn.GELU() (erf form)."""

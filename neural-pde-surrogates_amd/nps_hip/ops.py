@@ -12,7 +12,7 @@ from typing import List, NamedTuple, Optional, Sequence, Union
 
 import torch
 
-from . import Conv2dArgs, Conv3dArgs, PackJob, Src as _CSrc, Src3 as _CSrc3, check, lib, ptr, stream_ptr
+from . import Conv2dArgs, Conv3dArgs, PackJob, Wgrad3dArgs, Src as _CSrc, Src3 as _CSrc3, check, lib, ptr, stream_ptr
 
 GELU = 1
 
@@ -1370,6 +1370,93 @@ def conv3d(srcs: Sequence[Src3], frame_dhw, wpack: torch.Tensor, bias: Optional[
                            ("bf16_3d" if a.bf16 else "f32_3d", K ** 3, 4), nbytes))
     else:
         check(lib.nps_conv3d_fwd(ctypes_byref(a), stream_ptr()), "conv3d")
+    return out
+
+
+# ---- 3-D conv backward: weight derivations (torch ops on the parameter, any device), weight gradient, layout helpers
+def conv3d_dgrad_weight(w: torch.Tensor) -> torch.Tensor:
+    """nn.Conv3d weight (Cout, Cin, K, K, K) -> the stride-1 input gradient's conv weight (Cin, Cout, K, K, K): all
+    three taps flipped, channels swapped.  dx = conv3d(dy extended by K - 1 - p per side, this) for a conv padded
+    by p (zeros), or the circular conv of dy for circular 'same' padding."""
+    return w.detach().flip(2, 3, 4).transpose(0, 1).contiguous()
+
+
+def conv3d_s2_dgrad_weight(w: torch.Tensor) -> torch.Tensor:
+    """nn.Conv3d weight (Cout, Cin, 3, 3, 3) of a stride-2 conv -> the (Cout, Cin, 4, 4, 4) nn.ConvTranspose3d
+    weight whose k4/s2 transposed conv of dy is the input gradient (shifted by the conv's padding): the adjoint is
+    a k3/s2 transposed conv, i.e. a k4/s2 one whose fourth tap per axis is zero."""
+    return torch.nn.functional.pad(w.detach(), (0, 1, 0, 1, 0, 1)).contiguous()
+
+
+def conv_transpose3d_dgrad_weight(w: torch.Tensor) -> torch.Tensor:
+    """nn.ConvTranspose3d weight (Cin, Cout, 4, 4, 4) of a k4/s2 transposed conv -> the (Cin, 8 Cout, 2, 2, 2) conv
+    weight of its input gradient over the space-to-depth of dy (space_to_depth3d): channel ((rd*2 + rh)*2 + rw)*Cout
+    + co, tap (td, th, tw) holds w[ci, co, 2 td + rd, 2 th + rh, 2 tw + rw]."""
+    Cin, Cout = w.shape[:2]
+    return (w.detach().reshape(Cin, Cout, 2, 2, 2, 2, 2, 2).permute(0, 3, 5, 7, 1, 2, 4, 6)
+            .reshape(Cin, 8 * Cout, 2, 2, 2).contiguous())
+
+
+def _wgrad3d_args(a: torch.Tensor, x: torch.Tensor, K: int, stride: int, circ: int, zpad: int) -> Wgrad3dArgs:
+    for t in (a, x):
+        if t.dtype != torch.float32 or t.dim() != 5 or not t.is_contiguous():
+            raise RuntimeError(f"nps_hip conv3d_wgrad: contiguous fp32 NDHWC tensors, got {t.dtype} {tuple(t.shape)}")
+    if a.shape[0] != x.shape[0]:
+        raise RuntimeError("nps_hip conv3d_wgrad: a and x must share the batch")
+    p = Wgrad3dArgs()
+    p.a, (p.B, p.Da, p.Ha, p.Wa, p.M) = ptr(a), a.shape
+    p.x, (_, p.Dx, p.Hx, p.Wx, p.N) = ptr(x), x.shape
+    p.K, p.stride, p.circ, p.zpad = K, stride, circ, zpad
+    return p
+
+
+def conv3d_wgrad_splits(a: torch.Tensor, x: torch.Tensor, K: int, stride=1, circ=0, zpad=0) -> int:
+    """How many work-groups share each (m tile, n tile, tap group)'s voxel reduction in conv3d_wgrad's launch."""
+    p = _wgrad3d_args(a, x, K, stride, circ, zpad)
+    p.g = p.a  # (the plan only needs a non-NULL pointer)
+    n = lib.nps_conv3d_wgrad_splits(ctypes_byref(p))
+    check(0 if n > 0 else n, "conv3d_wgrad_splits")
+    return n
+
+
+def conv3d_wgrad(a: torch.Tensor, x: torch.Tensor, K: int, stride=1, circ=0, zpad=0,
+                 g: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """g[M][N][K][K][K] (+)= sum over a's voxels p of a[p][m] * Xext[p*stride + tap][n] (nps_conv3d_wgrad, exact fp32
+    MFMA): x (B, Dx, Hx, Wx, N) extended per side by `circ` circular then `zpad` zero voxels, a (B, Da, Ha, Wa, M) of
+    the valid K^3 / stride conv's output extent.  Without g a zero-filled one is allocated; a given g is added to."""
+    p = _wgrad3d_args(a, x, K, stride, circ, zpad)
+    if g is None:
+        g = torch.zeros((p.M, p.N, K, K, K), dtype=torch.float32, device=a.device)
+    elif g.dtype != torch.float32 or not g.is_contiguous() or g.numel() != p.M * p.N * K ** 3:
+        raise RuntimeError("nps_hip conv3d_wgrad: g must be contiguous fp32 [M][N][K][K][K]")
+    p.g = ptr(g)
+    check(lib.nps_conv3d_wgrad(ctypes_byref(p), stream_ptr()), "conv3d_wgrad")
+    return g
+
+
+def space_to_depth3d(x: torch.Tensor, Dq: int, Hq: int, Wq: int) -> torch.Tensor:
+    """(B, D, H, W, C) fp32 -> (B, Dq, Hq, Wq, 8 C): channel ((rd*2 + rh)*2 + rw)*C + c = x[2 dq + rd, 2 hq + rh,
+    2 wq + rw, c] (0 outside x)."""
+    B, D, H, W, C = x.shape
+    out = torch.empty((B, Dq, Hq, Wq, 8 * C), dtype=torch.float32, device=x.device)
+    check(lib.nps_space_to_depth3d(ptr(x), ptr(out), B, D, H, W, C, Dq, Hq, Wq, stream_ptr()), "space_to_depth3d")
+    return out
+
+
+def circular_pad3d(x: torch.Tensor, pad: int) -> torch.Tensor:
+    """(B, D, H, W, C) fp32 -> circularly padded by `pad` voxels per side of every axis."""
+    B, D, H, W, C = x.shape
+    out = torch.empty((B, D + 2 * pad, H + 2 * pad, W + 2 * pad, C), dtype=torch.float32, device=x.device)
+    check(lib.nps_circular_pad3d(ptr(x), ptr(out), B, D, H, W, C, pad, stream_ptr()), "circular_pad3d")
+    return out
+
+
+def circular_fold3d(gp: torch.Tensor, pad: int) -> torch.Tensor:
+    """The adjoint of circular_pad3d: (B, D + 2 pad, H + 2 pad, W + 2 pad, C) -> the wrap-sum (B, D, H, W, C)."""
+    B, Dp, Hp, Wp, C = gp.shape
+    D, H, W = Dp - 2 * pad, Hp - 2 * pad, Wp - 2 * pad
+    out = torch.empty((B, D, H, W, C), dtype=torch.float32, device=gp.device)
+    check(lib.nps_circular_fold3d(ptr(gp), ptr(out), B, D, H, W, C, pad, stream_ptr()), "circular_fold3d")
     return out
 
 
