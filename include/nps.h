@@ -661,6 +661,14 @@ size_t nps_conv3d_packed_bytes(int Cout, int Cin, int K, int transposed, int bf1
 int nps_conv3d_pack_weights(const float* w, void* wpack, int Cout, int Cin, int K, int transposed, int bf16,
                             void* stream);
 int nps_conv3d_fwd(const nps_conv3d_t* a, void* stream);
+/* Test hooks (host code only).  nps_conv3d_route writes into buf[n] the name of the kernel instantiation
+ * nps_conv3d_fwd would launch for *a — "conv3d_kernel<bf16|f32,K,S,TH,SIMPLE|GENERAL,REG|REG_O4|DMA|DMA_O4>" or
+ * "conv3d_1x1_kernel<NCB,NCH,PRO|PLAIN>" — through the same argument checks and dispatch, without a launch or
+ * any other HIP call (the pointers in *a are only compared with NULL).  nps_conv3d_1x1_set_grid: run the bf16
+ * 1x1x1 kernel on `wgs` work-groups per sample (> 0; 0 = one resident round, the default), so every wave walks
+ * several tiles of a small volume. */
+int nps_conv3d_route(const nps_conv3d_t* a, char* buf, int n);
+int nps_conv3d_1x1_set_grid(long wgs);
 /* act(GN(frame)) of a's core frame (sources, GroupNorm prologue, pre_act) materialised once as
  * out[B][Dc][Hc][Wc][Cpad] (channels >= Cin zero, Cpad % 8 == 0): the conv that follows reads one aligned
  * source without a prologue (the fused prologue recomputes each element for every depth tap and halo). */

@@ -15,6 +15,9 @@
 // so the ds_read_b128 B / A fragment reads of 32 consecutive rows are bank-conflict free.
 #include "nps_common.hpp"
 
+#include <cstdarg>
+#include <cstdio>
+
 namespace {
 
 typedef unsigned short bf16_t;
@@ -1179,8 +1182,28 @@ bool c3d_1x1_eligible(const nps_conv3d_t& a) {
     return a.nsrc <= 2;
 }
 
+// nps_conv3d_route: the dispatch below runs as for a launch, and the launcher it ends in writes the name of its
+// kernel instantiation here instead of launching (host arithmetic only: no HIP call is made)
+struct Route {
+    char* buf;
+    int n;
+};
+int route_name(const Route& q, const char* fmt, ...) __attribute__((format(printf, 2, 3)));
+int route_name(const Route& q, const char* fmt, ...) {
+    va_list ap;
+    va_start(ap, fmt);
+    const int len = vsnprintf(q.buf, (size_t)q.n, fmt, ap);
+    va_end(ap);
+    NPS_CHECK_ARG(len >= 0 && len < q.n, "conv3d_route: the name needs %d bytes, the buffer has %d", len + 1, q.n);
+    return 0;
+}
+
+// test hook (nps_conv3d_1x1_set_grid): work-groups per sample of the 1x1x1 kernel's grid (> 0)
+long g_1x1_grid_override = 0;
+
 template <int NCB, int NCH, bool PRO>
-int launch_1x1(const nps_conv3d_t& a, int nchunk, hipStream_t s) {
+int launch_1x1(const nps_conv3d_t& a, int nchunk, hipStream_t s, const Route* q) {
+    if (q != nullptr) return route_name(*q, "conv3d_1x1_kernel<%d,%d,%s>", NCB, NCH, PRO ? "PRO" : "PLAIN");
     const size_t lds = (size_t)nchunk * NCB * 32 * 32 + NCB * 32 * sizeof(float) + 2 * (size_t)nchunk * 16 * sizeof(float) +
                        8 * sizeof(double);
     NPS_CHECK_ARG(lds <= 160 * 1024, "conv3d (1x1x1): %zu B of LDS", lds);
@@ -1209,6 +1232,7 @@ int launch_1x1(const nps_conv3d_t& a, int nchunk, hipStream_t s) {
         occ = 2;
     const long resident = (long)ncu * occ;
     long per = (resident + a.B - 1) / a.B;
+    if (g_1x1_grid_override > 0) per = g_1x1_grid_override;  // (test hook: every wave walks several tiles)
     if (per > (ntv + 3) / 4) per = (ntv + 3) / 4;
     conv3d_1x1_kernel<NCB, NCH, PRO><<<dim3((unsigned)per, (unsigned)a.B), 256, lds, s>>>(a, nchunk);
     NPS_CHECK_LAUNCH("conv3d (1x1x1)");
@@ -1216,16 +1240,20 @@ int launch_1x1(const nps_conv3d_t& a, int nchunk, hipStream_t s) {
 }
 
 template <bool PRO>
-int dispatch_1x1(const nps_conv3d_t& a, int nchunk, hipStream_t s) {
+int dispatch_1x1(const nps_conv3d_t& a, int nchunk, hipStream_t s, const Route* q) {
     const bool w4 = a.Cout > 64;
-    if (nchunk <= 5) return w4 ? launch_1x1<4, 5, PRO>(a, nchunk, s) : launch_1x1<2, 5, PRO>(a, nchunk, s);
-    if (nchunk <= 9) return w4 ? launch_1x1<4, 9, PRO>(a, nchunk, s) : launch_1x1<2, 9, PRO>(a, nchunk, s);
-    return w4 ? launch_1x1<4, 16, PRO>(a, nchunk, s) : launch_1x1<2, 16, PRO>(a, nchunk, s);
+    if (nchunk <= 5) return w4 ? launch_1x1<4, 5, PRO>(a, nchunk, s, q) : launch_1x1<2, 5, PRO>(a, nchunk, s, q);
+    if (nchunk <= 9) return w4 ? launch_1x1<4, 9, PRO>(a, nchunk, s, q) : launch_1x1<2, 9, PRO>(a, nchunk, s, q);
+    return w4 ? launch_1x1<4, 16, PRO>(a, nchunk, s, q) : launch_1x1<2, 16, PRO>(a, nchunk, s, q);
 }
 
 template <typename T, int K, int S, int TH, bool SIMPLE, Form F = Form::REG>
-int launch(const nps_conv3d_t& a, int nchunk, int ntile, hipStream_t s) {
+int launch(const nps_conv3d_t& a, int nchunk, int ntile, hipStream_t s, const Route* q) {
     constexpr bool dma = F == Form::DMA || F == Form::DMA_O4;  // one stage buffer
+    if (q != nullptr)
+        return route_name(*q, "conv3d_kernel<%s,%d,%d,%d,%s,%s>", sizeof(T) == 2 ? "bf16" : "f32", K, S, TH,
+                          SIMPLE ? "SIMPLE" : "GENERAL",
+                          F == Form::REG ? "REG" : (F == Form::REG_O4 ? "REG_O4" : (F == Form::DMA ? "DMA" : "DMA_O4")));
     const auto kern = [] {  // (if constexpr: only the chosen kernel is instantiated)
         if constexpr (F == Form::REG) return conv3d_kernel<T, K, S, TH, SIMPLE>;
         else if constexpr (F == Form::REG_O4) return conv3d_kernel_o4r<T, K, S, TH, SIMPLE>;
@@ -1256,7 +1284,7 @@ bool simple_frame(const nps_conv3d_t& a) {
 }
 
 template <typename T>
-int dispatch(const nps_conv3d_t& a, int nchunk, int ntile, hipStream_t s) {
+int dispatch(const nps_conv3d_t& a, int nchunk, int ntile, hipStream_t s, const Route* q) {
     const bool sim = simple_frame(a);
     // bf16 fast-path frames: stage copies by LDS-DMA into one stage buffer — three work-groups per CU (3x3x3), four
     // for the register-light 2x2x2 phases (held to 4 waves per SIMD).  NPS_C3D_GLDS=0 (test-only):
@@ -1264,24 +1292,24 @@ int dispatch(const nps_conv3d_t& a, int nchunk, int ntile, hipStream_t s) {
     static const bool glds = nps::env_flag("NPS_C3D_GLDS", true);
     if constexpr (sizeof(T) == 2)
         if (sim && glds) {
-            if (a.K == 3 && a.stride == 1) return launch<T, 3, 1, 8, true, Form::DMA>(a, nchunk, ntile, s);
-            if (a.K == 3 && a.stride == 2) return launch<T, 3, 2, 4, true, Form::DMA>(a, nchunk, ntile, s);
-            if (a.K == 2 && a.stride == 1) return launch<T, 2, 1, 8, true, Form::DMA_O4>(a, nchunk, ntile, s);
+            if (a.K == 3 && a.stride == 1) return launch<T, 3, 1, 8, true, Form::DMA>(a, nchunk, ntile, s, q);
+            if (a.K == 3 && a.stride == 2) return launch<T, 3, 2, 4, true, Form::DMA>(a, nchunk, ntile, s, q);
+            if (a.K == 2 && a.stride == 1) return launch<T, 2, 1, 8, true, Form::DMA_O4>(a, nchunk, ntile, s, q);
         }
     if (a.K == 3 && a.stride == 1)
-        return sim ? launch<T, 3, 1, 8, true>(a, nchunk, ntile, s) : launch<T, 3, 1, 8, false>(a, nchunk, ntile, s);
+        return sim ? launch<T, 3, 1, 8, true>(a, nchunk, ntile, s, q) : launch<T, 3, 1, 8, false>(a, nchunk, ntile, s, q);
     if (a.K == 3 && a.stride == 2)
-        return sim ? launch<T, 3, 2, 4, true>(a, nchunk, ntile, s) : launch<T, 3, 2, 4, false>(a, nchunk, ntile, s);
+        return sim ? launch<T, 3, 2, 4, true>(a, nchunk, ntile, s, q) : launch<T, 3, 2, 4, false>(a, nchunk, ntile, s, q);
     if (a.K == 2 && a.stride == 1)
-        return sim ? launch<T, 2, 1, 8, true>(a, nchunk, ntile, s) : launch<T, 2, 1, 8, false>(a, nchunk, ntile, s);
+        return sim ? launch<T, 2, 1, 8, true>(a, nchunk, ntile, s, q) : launch<T, 2, 1, 8, false>(a, nchunk, ntile, s, q);
     if (a.K == 1 && a.stride == 1) {
         // bf16 multi-source 1x1x1 (the C5 shortcuts over cat(h, skip, vb)): a streaming kernel, held to four waves
         // per SIMD (four work-groups per CU, 128 VGPRs): (64, 64, 4) -> 64 at 16x128^2 471 -> 385 us, bit-identical
         // (profiles/r6/experiments/c5_conv3d_glds_ab.txt); NPS_C3D_K1O4=0 (test-only): three work-groups
         static const bool k1o4 = nps::env_flag("NPS_C3D_K1O4", true);
         if constexpr (sizeof(T) == 2)
-            if (!sim && k1o4) return launch<T, 1, 1, 8, false, Form::REG_O4>(a, nchunk, ntile, s);
-        return sim ? launch<T, 1, 1, 8, true>(a, nchunk, ntile, s) : launch<T, 1, 1, 8, false>(a, nchunk, ntile, s);
+            if (!sim && k1o4) return launch<T, 1, 1, 8, false, Form::REG_O4>(a, nchunk, ntile, s, q);
+        return sim ? launch<T, 1, 1, 8, true>(a, nchunk, ntile, s, q) : launch<T, 1, 1, 8, false>(a, nchunk, ntile, s, q);
     }
     NPS_CHECK_ARG(false, "conv3d: K=%d stride=%d not supported (K in {1,2,3}, stride 2 only for K=3)", a.K, a.stride);
 }
@@ -1325,7 +1353,9 @@ extern "C" int nps_conv3d_pack_weights(const float* w, void* wpack, int Cout, in
     return 0;
 }
 
-extern "C" int nps_conv3d_fwd(const nps_conv3d_t* ap, void* stream) {
+namespace {
+// nps_conv3d_fwd (q == nullptr), or with q the name of the kernel instantiation it would launch (nps_conv3d_route)
+int conv3d_run(const nps_conv3d_t* ap, void* stream, const Route* q) {
     NPS_CHECK_ARG(ap != nullptr, "conv3d: null args");
     const nps_conv3d_t& a = *ap;
     if (check_frame(a, "conv3d") < 0) return -1;
@@ -1347,9 +1377,24 @@ extern "C" int nps_conv3d_fwd(const nps_conv3d_t* ap, void* stream) {
     const int nchunk = (a.Cin + 15) / 16, ntile = (a.Cout + 63) / 64;
     hipStream_t s = (hipStream_t)stream;
     if (c3d_1x1_eligible(a))
-        return (a.gn_stats != nullptr || a.pre_act != 0) ? dispatch_1x1<true>(a, nchunk, s)
-                                                         : dispatch_1x1<false>(a, nchunk, s);
-    return a.bf16 ? dispatch<bf16_t>(a, nchunk, ntile, s) : dispatch<float>(a, nchunk, ntile, s);
+        return (a.gn_stats != nullptr || a.pre_act != 0) ? dispatch_1x1<true>(a, nchunk, s, q)
+                                                         : dispatch_1x1<false>(a, nchunk, s, q);
+    return a.bf16 ? dispatch<bf16_t>(a, nchunk, ntile, s, q) : dispatch<float>(a, nchunk, ntile, s, q);
+}
+}  // namespace
+
+extern "C" int nps_conv3d_fwd(const nps_conv3d_t* ap, void* stream) { return conv3d_run(ap, stream, nullptr); }
+
+extern "C" int nps_conv3d_route(const nps_conv3d_t* ap, char* buf, int n) {
+    NPS_CHECK_ARG(buf != nullptr && n > 0, "conv3d_route: no buffer");
+    buf[0] = 0;
+    const Route q = {buf, n};
+    return conv3d_run(ap, nullptr, &q);
+}
+
+extern "C" int nps_conv3d_1x1_set_grid(long wgs) {
+    g_1x1_grid_override = wgs > 0 ? wgs : 0;
+    return 0;
 }
 
 extern "C" int nps_frame_pack3d(const nps_conv3d_t* ap, void* out, int Cpad, void* stream) {

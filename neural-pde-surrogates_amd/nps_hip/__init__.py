@@ -220,6 +220,8 @@ _SIGS = {
     "nps_conv3d_packed_bytes": (_sz, [_i, _i, _i, _i, _i]),
     "nps_conv3d_pack_weights": (_i, [_vp, _vp, _i, _i, _i, _i, _i, _vp]),
     "nps_conv3d_fwd": (_i, [ctypes.POINTER(Conv3dArgs), _vp]),
+    "nps_conv3d_route": (_i, [ctypes.POINTER(Conv3dArgs), ctypes.c_char_p, _i]),
+    "nps_conv3d_1x1_set_grid": (_i, [ctypes.c_long]),
     "nps_gn_stats3d": (_i, [ctypes.POINTER(Conv3dArgs), _i, _vp, _vp]),
     "nps_frame_pack3d": (_i, [ctypes.POINTER(Conv3dArgs), _vp, _i, _vp]),
     # 3-D conv backward

@@ -262,11 +262,13 @@ _STREAM_CASES.append(pytest.param(128, (256,), ((0, 0, 0),), 1, (4, 16, 32), id=
 
 @pytest.mark.parametrize("cout,chans,offs,B,dhw", _STREAM_CASES)
 def test_conv3d_1x1x1_bf16_streaming(cout, chans, offs, B, dhw):
-    """The bf16 1x1x1 kernel (conv3d_1x1_kernel: weights resident in LDS, every K-step's load of a 32-voxel tile in
-    flight at once): the ResidualBlock shortcut over cat(h, crop_Nd(skip), crop_Nd(vb)) at Cin 68 / 132 / 200 (5, 9
-    and 16 K-step register sets), Cout 64 / 96 / 128 (2 and 4 channel blocks), a volume that is not a multiple of
-    32 voxels; bias, out_stats; against fp64 on the bf16-rounded operands, and the moments against a gn_stats3d pass.
-    Cin 256 -> Cout 128 is the one shape whose resident weights need more than 64 KiB of LDS."""
+    """The bf16 1x1x1 convs of the ResidualBlock shortcut over cat(h, crop_Nd(skip), crop_Nd(vb)), Cout 64 / 96 / 128,
+    a volume that is not a multiple of 32 voxels; bias, out_stats; against fp64 on the bf16-rounded operands, and the
+    moments against a gn_stats3d pass.  The two-source frames (Cin 68 and 200: 5 and 16 K-step register sets, 2 and 4
+    channel blocks) run conv3d_1x1_kernel (weights resident in LDS, every K-step's load of a 32-voxel tile in flight at
+    once); the three-source 132-channel frame is refused by c3d_1x1_eligible and runs the generic conv3d_kernel at
+    four waves per SIMD, so no row here reaches the 9 K-step sets (tests/test_gpu_conv3d_fwd.py does, on 128 + 4
+    channels).  Cin 256 -> Cout 128 is the one shape whose resident weights need more than 64 KiB of LDS."""
     from nps_hip import ops
     torch.manual_seed(13)
     xs = []
