@@ -706,6 +706,30 @@ int nps_space_to_depth3d(const float* x, float* out, int B, int D, int H, int W,
 int nps_circular_pad3d(const float* x, float* out, int B, int D, int H, int W, int C, int pad, void* stream);
 int nps_circular_fold3d(const float* gp, float* gx, int B, int D, int H, int W, int C, int pad, void* stream);
 
+/* ---- 3-D frame of the differentiable U-Net walk (fp32 only: a->bf16 != 0 is refused) ----
+ * The frame is described by nps_conv3d_t's sources and offsets, B, Dc, Hc, Wc, Cin, the GroupNorm fields and pre_act;
+ * its conv fields are ignored.
+ *
+ * nps_frame3d_fwd: out[B][Dc][Hc][Wc][Cin] = act(GN(frame)) with exactly Cin channels (no channel padding; the erf
+ * GELU whose derivative the backward uses).  Without prologue and activation this is crop_Nd in 3-D. */
+int nps_frame3d_fwd(const nps_conv3d_t* a, float* out, void* stream);
+/* Its backward, the 3-D form of nps_frame_pack_bwd2: gy = dL/d(frame) [B][Dc][Hc][Wc][Cin]; gy_plain (or NULL) = the
+ * gradient of the un-normalised concatenation of the same sources, shaped like gy, added into dsrc in the same pass.
+ * dsrc[i] (shape of source i; a NULL entry is skipped) receives source i's gradient, exactly 0 at its voxels
+ * outside the frame; dgamma / dbeta [Cin] are written when the frame has a GroupNorm; work = [B][2][Cin] fp64 that
+ * holds zeros on entry.  The group size N counts the whole frame (uncovered positions are zeros that take part in the
+ * statistics, as in nps_gn_stats3d). */
+int nps_frame3d_bwd(const nps_conv3d_t* a, const float* gy, const float* gy_plain, float* const* dsrc, float* dgamma,
+                    float* dbeta, double* work, void* stream);
+/* out = base + crop_Nd(src) placed at (off_d, off_h, off_w) in one pass (out, base: [B][Do][Ho][Wo][C]; src:
+ * [B][Ds][Hs][Ws][C]); offsets of either sign per axis (> 0 zero-pads, < 0 crops); any C. */
+int nps_add_at_copy3d(float* out, const float* base, const float* src, int B, int Do, int Ho, int Wo, int Ds, int Hs,
+                      int Ws, int C, int off_d, int off_h, int off_w, void* stream);
+/* Test hook (host code only, no HIP call): 1 and the frame coordinates (fd, fh, fw) when voxel (d, h, w) of source
+ * si lies inside a's core frame, 0 when it lies outside, < 0 on bad arguments or if the two directions of the
+ * kernels' voxel decode disagree.  It runs the same __host__ __device__ index functions as the three entries above. */
+int nps_frame3d_locate(const nps_conv3d_t* a, int si, int d, int h, int w, int* fd, int* fh, int* fw);
+
 /* ---- U-Net self-attention (proc_unet_modern.py:292-317), never materialising the N x N scores ----
  * Layouts, exactly as the qkv projection writes them (no q / k / v split copies):
  *   qkv, dqkv [B][N][heads][3*dk]  (per head [q | k | v], dk floats each)

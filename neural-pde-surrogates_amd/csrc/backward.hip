@@ -224,10 +224,7 @@ __global__ void channel_sums4_kernel(const float* __restrict__ x, long rows, int
 }
 
 // ------------------------------------------------------------------------------ element-wise
-__device__ __forceinline__ float gelu_grad(float z) {
-    // d/dz [0.5 z (1 + erf(z/sqrt2))] = Phi(z) + z phi(z)
-    return 0.5f * (1.0f + erff(z * 0.70710678118654752440f)) + z * 0.39894228040143267794f * expf(-0.5f * z * z);
-}
+__device__ __forceinline__ float gelu_grad(float z) { return nps::gelu_erf_grad(z); }
 
 __global__ void gelu_kernel(const float* __restrict__ x, float* __restrict__ y, long n) {
     for (long i = (long)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (long)gridDim.x * blockDim.x)

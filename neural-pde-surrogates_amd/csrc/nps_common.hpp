@@ -46,6 +46,11 @@ __device__ __forceinline__ float gelu_erf(float x) {
     return 0.5f * x * (1.0f + erff(x * 0.70710678118654752440f));
 }
 
+// its derivative: d/dz [0.5 z (1 + erf(z/sqrt2))] = Phi(z) + z phi(z)
+__device__ __forceinline__ float gelu_erf_grad(float z) {
+    return 0.5f * (1.0f + erff(z * 0.70710678118654752440f)) + z * 0.39894228040143267794f * expf(-0.5f * z * z);
+}
+
 // The same GELU with a branch-free erfc (Numerical Recipes' Chebyshev-fitted erfcc: fractional error < 1.2e-7
 // for every argument, so GELU keeps ~1e-7 relative accuracy on both tails): 0.5 x erfc(|x|/sqrt 2) for x < 0,
 // x - 0.5 x erfc(x/sqrt 2) otherwise; ~15 VALU (one v_rcp, one v_exp) instead of erff's branchy polynomial —

@@ -196,13 +196,23 @@ def to_ncdhw(y):
     return (ops.to_bf16(x) if bf else x).view(B, C, D, H, W)
 
 
+def ad_to_ndhwc(x):
+    """to_ndhwc of an fp32 tensor, differentiably: NCDHW -> NDHWC is the NCHW -> NHWC permutation of the
+    (B, C, D*H, W) view."""
+    B, C, D, H, W = x.shape
+    return ad.to_nhwc(x.reshape(B, C, D * H, W)).view(B, D, H, W, C)
+
+
+def ad_to_ncdhw(y):
+    """to_ncdhw of an fp32 tensor, differentiably."""
+    B, D, H, W, C = y.shape
+    return ad.to_nchw(y.reshape(B, D * H, W, C)).view(B, C, D, H, W)
+
+
 def _ad_ncdhw(fn, conv, x):
     """fn(conv, x) — ad.conv3d / ad.conv_transpose3d, on NDHWC — around the differentiable layout transposes of an
-    fp32 (B, C, D, H, W) tensor: NCDHW <-> NDHWC is the NCHW <-> NHWC permutation of the (B, C, D*H, W) view."""
-    B, C, D, H, W = x.shape
-    y = fn(conv, ad.to_nhwc(x.reshape(B, C, D * H, W)).view(B, D, H, W, C))
-    _, Do, Ho, Wo, Co = y.shape
-    return ad.to_nchw(y.view(B, Do * Ho, Wo, Co)).view(B, Co, Do, Ho, Wo)
+    fp32 (B, C, D, H, W) tensor."""
+    return ad_to_ncdhw(fn(conv, ad_to_ndhwc(x)))
 
 
 class _Packed3Mixin:
@@ -388,8 +398,8 @@ def get_upconv_with_right_spatial_dim(spatial_dim, in_channels, out_channels, **
 
 
 class Form(NamedTuple):
-    """One of the three ways the U-Net modules run on channels-last activations."""
-    run: str             # the per-module method: run / run_ad / run3d
+    """One of the four ways the U-Net modules run on channels-last activations."""
+    run: str             # the per-module method: run / run_ad / run3d / run_ad3d
     Src: type            # ops.Src / ops.Src3
     nd: int              # spatial dims: a map's size is shape[1:1 + nd]
     upsample: Callable   # (Upsample.conv, h) -> the transposed conv's output
@@ -406,6 +416,9 @@ def _upsample3d(conv, h):
 INFER2D = Form("run", ops.Src, 2, lambda conv, h: conv.run(h), ops.nchw_to_nhwc, ops.nhwc_to_nchw)
 AUTOGRAD2D = Form("run_ad", ops.Src, 2, ad.conv_transpose2d, ad.to_nhwc, ad.to_nchw)
 INFER3D = Form("run3d", ops.Src3, 3, _upsample3d, to_ndhwc, to_ncdhw)
+# fp32 training in 3-D.  run_form never picks it (the 3-D module boundaries refuse grad mode): UFNO.forward and the
+# NDHWC methods run_ad3d are its entries.
+AUTOGRAD3D = Form("run_ad3d", ops.Src3, 3, ad.conv_transpose3d, ad_to_ndhwc, ad_to_ncdhw)
 
 
 def run_form(mod, x, vb, fn):

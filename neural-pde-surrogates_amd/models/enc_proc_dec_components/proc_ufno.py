@@ -11,7 +11,7 @@ import torch
 from torch import nn
 
 from common.interfaces import D, M
-from models.common import activation_code, use_autograd, to_ndhwc, to_ncdhw
+from models.common import activation_code, use_autograd, to_ndhwc, to_ncdhw, ad_to_ndhwc, ad_to_ncdhw
 from models.enc_proc_dec_components.proc_fno import FNO_Layer
 from models.enc_proc_dec_components.proc_unet_modern import UNetModern
 from nps_hip import ops
@@ -105,11 +105,31 @@ class UFNO(nn.Module):
             h = ad.act(ad.add_at(h_fno, unet.run_ad(h, vb)), act)
         return h
 
+    def run_ad3d(self, h, vb):
+        """Differentiable form of run3d() on NDHWC fp32 (training): per block the FNO-3D layer on the frame of
+        (h, vb) — no offsets, so the 2-D frame of the (B, D*H, W, C) view — plus the 3-D U-Net, then the activation."""
+        if self.cond_mode != "concat":
+            raise NotImplementedError("U-FNO: only cond_mode='concat' runs on the MI355X path")
+        if self.num_spatial_dims != 3:
+            raise NotImplementedError("UFNO.run_ad3d: 3-D only")
+        act = activation_code(self.activation)
+        B, D, H, W = h.shape[:4]
+        flat = lambda t: t.view(t.shape[0], D * H, W, t.shape[4])  # noqa: E731
+        for fno, unet in zip(self.fno_layers, self.unet_layers):
+            srcs = [ops.Src(flat(h))] + ([ops.Src(flat(vb))] if vb is not None else [])
+            h_fno = fno.run_ad(ad.frame(srcs, (D * H, W)), D)
+            h = ad.act(ad.add_at(h_fno, flat(unet.run_ad3d(h, vb))), act).view(B, D, H, W, -1)
+        return h
+
     def forward(self, h: torch.Tensor, variables: torch.Tensor = None, variables_broadcast: torch.Tensor = None,
                 pos=None):
         if self.num_spatial_dims == 3:  # (B, C, D, H, W), fp32 or bf16 storage (C5)
             if use_autograd(self):
-                raise NotImplementedError("the 3-D U-FNO is inference-only on the MI355X path (C5 rollout)")
+                vb = variables_broadcast
+                if h.dtype != torch.float32 or (vb is not None and vb.dtype != torch.float32):
+                    raise NotImplementedError("the 3-D U-FNO differentiates fp32 tensors only: use fp32 for training "
+                                              "(bf16 storage is the inference path)")
+                return ad_to_ncdhw(self.run_ad3d(ad_to_ndhwc(h), ad_to_ndhwc(vb) if vb is not None else None))
             vb = to_ndhwc(variables_broadcast) if variables_broadcast is not None else None
             if vb is not None and vb.dtype != h.dtype:  # conditioning in the activations' storage dtype
                 vb = ops.to_bf16(vb) if h.dtype == torch.bfloat16 else ops.to_f32(vb)

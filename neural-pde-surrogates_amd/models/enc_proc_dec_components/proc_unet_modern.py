@@ -10,14 +10,15 @@ chain of fused HIP launches on NHWC tensors:
   * the final GN(8)+GELU+conv+crop is one conv launch whose epilogue can also
     fuse the U-FNO `GELU(h_fno + h_unet)` (proc_ufno.py:118).
 
-The model runs in three forms (models.common.Form): 2-D inference (`run`, the fused launches above), 2-D
-autograd (`run_ad`, the same kernels unfused plus their backward kernels) and 3-D inference (`run3d`, NDHWC).
+The model runs in four forms (models.common.Form): 2-D inference (`run`, the fused launches above), 2-D
+autograd (`run_ad`, the same kernels unfused plus their backward kernels), 3-D inference (`run3d`, NDHWC) and 3-D
+autograd (`run_ad3d`, NDHWC fp32).
 The down / middle / up traversal is written once, `UNetModern._walk(form, h, vb)`, and so is each
 Down / MiddleBlock body (`_run(form, x, vb)`); a form names the per-module method, the source tuple, the number
 of spatial dims and how an Upsample is applied.  What differs by algorithm stays written per form: the three
-ResidualBlock bodies, AttentionBlock, Downsample and the final conv stage of `UNetModern.run / run_ad / run3d`.
-Every forward() enters through models.common.run_form, which picks the form, converts the layout in and out and
-refuses 3-D under autograd.
+ResidualBlock bodies, AttentionBlock, Downsample and the final conv stage of `UNetModern.run / run_ad / run3d /
+run_ad3d`.  Every forward() enters through models.common.run_form, which picks the form, converts the layout in and
+out and refuses 3-D under autograd: the 3-D autograd form is entered through UFNO.forward or by calling run_ad3d.
 """
 from typing import List, Tuple, Union
 
@@ -26,7 +27,7 @@ from torch import nn
 
 from common.interfaces import D, M
 from models.common import (get_conv_with_right_spatial_dim, get_upconv_with_right_spatial_dim, crop_offsets,
-                           activation_code, run_form, INFER2D, AUTOGRAD2D, INFER3D)
+                           activation_code, run_form, INFER2D, AUTOGRAD2D, INFER3D, AUTOGRAD3D)
 from nps_hip import ops
 from nps_hip import autograd as ad
 from pdes import PDE
@@ -199,6 +200,13 @@ class UNetModern(nn.Module):
             ops.attach_stats(out, st)
         return out
 
+    def run_ad3d(self, h, vb):
+        """Differentiable NDHWC fp32 forward of the 3-D U-Net (training): run3d() as unfused HIP ops."""
+        h, h_shape = self._walk(AUTOGRAD3D, h, vb)
+        norm = self.norm if isinstance(self.norm, nn.GroupNorm) else None
+        y = ad.conv3d(self.final, ad.frame3d([ops.Src3(h)], h.shape[1:4], norm, activation_code(self.activation)))
+        return ad.crop3d(y, h_shape[1:4], crop_offsets(y.shape[1:4], h_shape[1:4]))
+
     def forward(self, h: torch.Tensor, variables_broadcast: torch.Tensor = None, pos=None):
         assert h.dim() == 2 + self.num_spatial_dims
         return run_form(self, h, variables_broadcast, lambda form, h, vb: getattr(self, form.run)(h, vb))
@@ -339,6 +347,20 @@ class ResidualBlock(nn.Module):
             sc = ad.conv2d(self.shortcut, xin if xin is not None else ad.frame(srcs, (H, W)))
         h2 = ad.conv2d(self.conv2, ad.frame([ops.Src(h1)], h1.shape[1:3], n2, act))
         return ad.add_at(sc, h2, crop_offsets(h2.shape[1:3], sc.shape[1:3]))
+
+    def run_ad3d(self, srcs, frame_dhw):
+        """run_ad() in 3-D on NDHWC fp32 Src3 sources: frame pair -> conv1 -> frame -> conv2, added into the
+        shortcut at its crop_Nd offset."""
+        act = activation_code(self.activation)
+        n1 = self.norm1 if isinstance(self.norm1, nn.GroupNorm) else None
+        n2 = self.norm2 if isinstance(self.norm2, nn.GroupNorm) else None
+        if isinstance(self.shortcut, nn.Identity):
+            _check_identity_input(srcs, frame_dhw)
+        f1, xin = ad.frame_pair3d(srcs, frame_dhw, n1, act)
+        h1 = ad.conv3d(self.conv1, f1)
+        sc = xin if isinstance(self.shortcut, nn.Identity) else ad.conv3d(self.shortcut, xin)
+        h2 = ad.conv3d(self.conv2, ad.frame3d([ops.Src3(h1)], h1.shape[1:4], n2, act))
+        return ad.add_at3d(sc, h2, crop_offsets(h2.shape[1:4], sc.shape[1:4]))
 
     def forward(self, x: torch.Tensor):
         return run_form(self, x, None, lambda form, x, _: getattr(self, form.run)(
@@ -528,6 +550,12 @@ class Downsample(nn.Module):
             ops.attach_stats(h, st)
         if vb is not None:
             vb = self.conv_variables_broadcast.run3d([ops.Src3(vb)], vb.shape[1:4])
+        return h, vb
+
+    def run_ad3d(self, x, vb):
+        h = ad.conv3d(self.conv, x)
+        if vb is not None:
+            vb = ad.conv3d(self.conv_variables_broadcast, vb)
         return h, vb
 
     def forward(self, x: torch.Tensor, variables_broadcast: torch.Tensor = None):

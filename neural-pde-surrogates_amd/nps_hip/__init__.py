@@ -230,6 +230,12 @@ _SIGS = {
     "nps_space_to_depth3d": (_i, [_vp, _vp, _i, _i, _i, _i, _i, _i, _i, _i, _vp]),
     "nps_circular_pad3d": (_i, [_vp, _vp, _i, _i, _i, _i, _i, _i, _vp]),
     "nps_circular_fold3d": (_i, [_vp, _vp, _i, _i, _i, _i, _i, _i, _vp]),
+    # 3-D frame of the differentiable U-Net walk
+    "nps_frame3d_fwd": (_i, [ctypes.POINTER(Conv3dArgs), _vp, _vp]),
+    "nps_frame3d_bwd": (_i, [ctypes.POINTER(Conv3dArgs), _vp, _vp, ctypes.POINTER(ctypes.c_void_p), _vp, _vp, _vp,
+                             _vp]),
+    "nps_add_at_copy3d": (_i, [_vp, _vp, _vp] + [_i] * 11 + [_vp]),
+    "nps_frame3d_locate": (_i, [ctypes.POINTER(Conv3dArgs), _i, _i, _i, _i] + [ctypes.POINTER(_i)] * 3),
     # U-Net self-attention (column softmax), flash-style
     "nps_attn_colstats": (_i, [_vp, _vp, _i, _i, _i, _i, ctypes.c_float, _vp]),
     "nps_attn_fwd": (_i, [_vp, _vp, _vp, _i, _i, _i, _i, ctypes.c_float, _vp]),

@@ -617,6 +617,129 @@ def conv_transpose3d(conv, x: torch.Tensor) -> torch.Tensor:
     return ConvTranspose3dFn.apply((conv.pad,), x, conv.weight, conv.bias)
 
 
+# ------------------------------------------------------------------------- 3-D frame (cat/crop/GN/GELU)
+def _frame3d_fwd(meta, gamma, beta, srcs):
+    """The forward shared by Frame3dFn / FramePair3dFn: (Src3 sources, GN or None, act(GN(frame)))."""
+    offsets, frame_dhw, groups, eps, act = meta
+    for t in srcs:
+        if t.dtype != torch.float32 or t.dim() != 5:
+            raise NotImplementedError(f"3-D frame: fp32 NDHWC sources only (use fp32 for training), got {t.dtype} "
+                                      f"{tuple(t.shape)}")
+    ss = [ops.Src3(_c(t), *o) for t, o in zip(srcs, offsets)]
+    gn = None
+    if gamma is not None:  # a pass over the frame (carried moments stay with the inference path)
+        gn = ops.GN(ops.gn_stats3d(ss, frame_dhw, groups), gamma.detach(), beta.detach(), groups, eps)
+    return ss, gn, ops.frame3d(ss, frame_dhw, gn, act)
+
+
+def _frame3d_save(ctx, meta, gamma, beta, gn, ss):
+    ctx.meta = meta
+    ctx.has_gn = gn is not None
+    ctx.save_for_backward(*([gamma, beta, gn.stats] if gn is not None else []), *[s.t for s in ss])
+
+
+def _frame3d_bwd(ctx, gout, gplain):
+    """Frame3dFn / FramePair3dFn backward: the sources' gradients (and the GroupNorm affine's) in one
+    nps_frame3d_bwd, gplain (the plain concatenation's gradient, or None) added inside it."""
+    offsets, frame_dhw, groups, eps, act = ctx.meta
+    saved = ctx.saved_tensors
+    gn = None
+    if ctx.has_gn:
+        gamma, beta, stats = saved[:3]
+        gn = ops.GN(stats, gamma, beta, groups, eps)
+        saved = saved[3:]
+    ss = [ops.Src3(t, *o) for t, o in zip(saved, offsets)]
+    dsrc, dgamma, dbeta = ops.frame3d_bwd(ss, frame_dhw, gn, act, _c(gout), _c(gplain) if gplain is not None else None,
+                                          ctx.needs_input_grad[3:])
+    return (None, dgamma, dbeta, *dsrc)
+
+
+class Frame3dFn(torch.autograd.Function):
+    """act(GroupNorm(cat(crop_Nd(src_i)))) on NDHWC fp32 — FrameFn in 3-D (proc_unet_modern.py:245-247, :191 with
+    num_spatial_dims=3): offsets along D, H and W, exactly Cin channels."""
+
+    @staticmethod
+    def forward(ctx, meta, gamma, beta, *srcs):
+        ss, gn, out = _frame3d_fwd(meta, gamma, beta, srcs)
+        _frame3d_save(ctx, meta, gamma, beta, gn, ss)
+        return out
+
+    @staticmethod
+    def backward(ctx, gout):
+        return _frame3d_bwd(ctx, gout, None)
+
+
+class FramePair3dFn(torch.autograd.Function):
+    """(act(GroupNorm(cat(crop_Nd(src_i)))), cat(crop_Nd(src_i))) from one node — FramePairFn in 3-D: a ResidualBlock's
+    conv1 input and its shortcut's (or identity path's) input, so the backward adds the second output's gradient
+    inside the frame backward.  A single source covering the frame is returned as the plain output itself (a view)."""
+
+    @staticmethod
+    def forward(ctx, meta, gamma, beta, *srcs):
+        offsets, frame_dhw = meta[0], meta[1]
+        ss, gn, out = _frame3d_fwd(meta, gamma, beta, srcs)
+        ident = len(ss) == 1 and not any(offsets[0]) and tuple(srcs[0].shape[1:4]) == tuple(frame_dhw)
+        plain = srcs[0] if ident else ops.frame3d(ss, frame_dhw)
+        _frame3d_save(ctx, meta, gamma, beta, gn, ss)
+        return out, plain
+
+    @staticmethod
+    def backward(ctx, gout, gplain):
+        if gout is None:  # (only the plain output was used)
+            srcs = ctx.saved_tensors[(3 if ctx.has_gn else 0):]
+            gout = torch.zeros((srcs[0].shape[0], *ctx.meta[1], sum(t.shape[4] for t in srcs)), dtype=torch.float32,
+                               device=gplain.device)
+        return _frame3d_bwd(ctx, gout, gplain)
+
+
+def _frame3d_meta(srcs, frame_dhw, norm, act):
+    return (tuple((int(s.off_d), int(s.off_h), int(s.off_w)) for s in srcs), tuple(int(v) for v in frame_dhw),
+            norm.num_groups if norm is not None else 0, float(norm.eps) if norm is not None else 0.0, act)
+
+
+def frame_pair3d(srcs: Sequence[ops.Src3], frame_dhw, norm=None, act=0):
+    """(frame3d(srcs, norm, act), frame3d(srcs)) through FramePair3dFn: one frame backward for both consumers."""
+    return FramePair3dFn.apply(_frame3d_meta(srcs, frame_dhw, norm, act), norm.weight if norm is not None else None,
+                               norm.bias if norm is not None else None, *[s.t for s in srcs])
+
+
+def frame3d(srcs: Sequence[ops.Src3], frame_dhw, norm=None, act=0) -> torch.Tensor:
+    """Materialise the virtual NDHWC conv input frame (differentiably).  `norm` is an nn.GroupNorm or None."""
+    meta = _frame3d_meta(srcs, frame_dhw, norm, act)
+    if norm is None and act == 0 and len(srcs) == 1 and not any(meta[0][0]) \
+            and tuple(srcs[0].t.shape[1:4]) == meta[1]:
+        return srcs[0].t
+    return Frame3dFn.apply(meta, norm.weight if norm is not None else None, norm.bias if norm is not None else None,
+                           *[s.t for s in srcs])
+
+
+def crop3d(x: torch.Tensor, out_dhw, off) -> torch.Tensor:
+    """crop_Nd (common.py:20-34) in 3-D: place x at `off` inside a zero frame of size out_dhw."""
+    return frame3d([ops.Src3(x, *off)], out_dhw)
+
+
+class AddAt3dFn(torch.autograd.Function):
+    """base + crop_Nd(src) placed at `off` on NDHWC fp32 (the residual `crop_Nd(h) + shortcut`,
+    proc_unet_modern.py:250 in 3-D; off = (0, 0, 0) and equal sizes is a plain sum, proc_ufno.py:118)."""
+
+    @staticmethod
+    def forward(ctx, off, base, src):
+        ctx.off, ctx.src_dhw = off, tuple(src.shape[1:4])
+        return ops.add_at_copy3d(_c(base), _c(src), off)
+
+    @staticmethod
+    def backward(ctx, g):
+        g = _c(g)
+        gs = None
+        if ctx.needs_input_grad[2]:  # the adjoint of the placement: crop_Nd of g at the negated offsets
+            gs = ops.frame3d([ops.Src3(g, *(-o for o in ctx.off))], ctx.src_dhw)
+        return None, g, gs
+
+
+def add_at3d(base, src, off=(0, 0, 0)):
+    return AddAt3dFn.apply(tuple(int(o) for o in off), base, src)
+
+
 # ------------------------------------------------------------------------- element-wise
 class GeluFn(torch.autograd.Function):
     """nn.GELU() (erf form)."""

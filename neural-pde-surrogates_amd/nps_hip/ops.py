@@ -5,6 +5,7 @@ Activations are NHWC fp32 tensors of shape (B, H, W, C).  A conv input is a
 along channels, each placed at an offset of the frame (crop_Nd, cat), so no
 cat / pad / crop is ever materialised.
 """
+import ctypes
 import math
 import os
 import weakref
@@ -1316,6 +1317,63 @@ def frame_pack3d(srcs: Sequence[Src3], frame_dhw, gn: Optional[GN] = None, pre_a
     cpad = (a.Cin + 15) // 16 * 16
     out = torch.empty((a.B, a.Dc, a.Hc, a.Wc, cpad), dtype=srcs[0].t.dtype, device=srcs[0].t.device)
     check(lib.nps_frame_pack3d(ctypes_byref(a), ptr(out), cpad, stream_ptr()), "frame_pack3d")
+    return out
+
+
+def _fp32_frame3(a, what):
+    if a.bf16:
+        raise NotImplementedError(f"nps_hip {what}: fp32 only (the 3-D frames differentiate fp32 tensors; use fp32 "
+                                  "for training)")
+
+
+def frame3d(srcs: Sequence[Src3], frame_dhw, gn: Optional[GN] = None, pre_act=0) -> torch.Tensor:
+    """(B, Dc, Hc, Wc, Cin) fp32 = act(GN(virtual frame)) with exactly Cin channels (nps_frame3d_fwd): the frame of
+    the differentiable 3-D walk (the conv weight's own Cin, no channel padding, erf GELU).  Without gn and pre_act
+    this is crop_Nd in 3-D."""
+    a = _fill_frame3(Conv3dArgs(), srcs, frame_dhw)
+    _fp32_frame3(a, "frame3d")
+    _set_prologue(a, gn, pre_act)
+    out = torch.empty((a.B, a.Dc, a.Hc, a.Wc, a.Cin), dtype=torch.float32, device=srcs[0].t.device)
+    check(lib.nps_frame3d_fwd(ctypes_byref(a), ptr(out), stream_ptr()), "frame3d_fwd")
+    return out
+
+
+def frame3d_bwd(srcs: Sequence[Src3], frame_dhw, gn: Optional[GN], pre_act, gy: torch.Tensor,
+                gy_plain: Optional[torch.Tensor] = None, need: Optional[Sequence[bool]] = None):
+    """The backward of frame3d (nps_frame3d_bwd): (dsrc list, dgamma, dbeta) given gy = dL/d(frame) and gy_plain
+    (or None), the gradient of the plain concatenation of the same sources.  need[i] False: source i gets no
+    gradient (None).  dgamma / dbeta are None without a GroupNorm."""
+    a = _fill_frame3(Conv3dArgs(), srcs, frame_dhw)
+    _fp32_frame3(a, "frame3d_bwd")
+    _set_prologue(a, gn, pre_act)
+    shape = (a.B, a.Dc, a.Hc, a.Wc, a.Cin)
+    for g in (gy, gy_plain):
+        if g is not None and (tuple(g.shape) != shape or g.dtype != torch.float32 or not g.is_contiguous()):
+            raise RuntimeError(f"nps_hip frame3d_bwd: gradients must be contiguous fp32 {shape}, got {tuple(g.shape)}")
+    dgamma = dbeta = work = None
+    if gn is not None:
+        dgamma, dbeta = torch.empty_like(gn.gamma), torch.empty_like(gn.beta)
+        work = new_stats(a.B, gy, a.Cin)  # zero on entry: a slice of a zeroed chunk
+    need = [True] * len(srcs) if need is None else need
+    dsrc = [torch.empty_like(s.t) if need[i] else None for i, s in enumerate(srcs)]
+    arr = (ctypes.c_void_p * 3)(*[ptr(d) for d in dsrc] + [None] * (3 - len(dsrc)))
+    check(lib.nps_frame3d_bwd(ctypes_byref(a), ptr(gy), ptr(gy_plain), arr, ptr(dgamma), ptr(dbeta), ptr(work),
+                              stream_ptr()), "frame3d_bwd")
+    return dsrc, dgamma, dbeta
+
+
+def add_at_copy3d(base: torch.Tensor, src: torch.Tensor, off=(0, 0, 0)) -> torch.Tensor:
+    """base + crop_Nd(src) placed at `off` (per axis: > 0 zero-pads, < 0 crops), NDHWC fp32, one pass."""
+    for t in (base, src):
+        if t.dtype != torch.float32 or t.dim() != 5 or not t.is_contiguous():
+            raise RuntimeError(f"nps_hip add_at_copy3d: contiguous fp32 NDHWC tensors, got {t.dtype} {tuple(t.shape)}")
+    if base.shape[0] != src.shape[0] or base.shape[4] != src.shape[4]:
+        raise RuntimeError("nps_hip add_at_copy3d: base and src must share batch and channels")
+    B, Do, Ho, Wo, C = base.shape
+    out = torch.empty_like(base)
+    check(lib.nps_add_at_copy3d(ptr(out), ptr(base), ptr(src), B, Do, Ho, Wo, src.shape[1], src.shape[2],
+                                src.shape[3], C, int(off[0]), int(off[1]), int(off[2]), stream_ptr()),
+          "add_at_copy3d")
     return out
 
 
