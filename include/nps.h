@@ -521,6 +521,11 @@ int nps_conv2d_wgrad_x3(const nps_wgrad_t* p, const float* a_range, const float*
 /* The same, storing G = the weight gradient (g need not be zeroed beforehand) instead of adding to it. */
 int nps_conv2d_wgrad_x3_set(const nps_wgrad_t* p, const float* a_range, const float* x_range, float* ws,
                             void* stream);
+/* Test hook (host code only, launches nothing): the launch plan nps_conv2d_wgrad_x3 would use for *p.
+ * out[0] kernel (0: wgrad_x3_kernel<KH,KW>, 1: wgrad1_wide_kernel, 2: wgrad2_wide_kernel), out[1] ntiles,
+ * out[2] base (m x n tiles), out[3] n_nt, out[4] splits, out[5] tiles per split, out[6] remap, out[7] grid.
+ * < 0 where nps_conv2d_wgrad_x3 would refuse p. */
+int nps_conv2d_wgrad_x3_plan(const nps_wgrad_t* p, int out[8]);
 /* out[c] += sum over `rows` rows of x[row][c] (conv bias gradients; parameter-partial reductions) */
 int nps_channel_sums(const float* x, long rows, int C, float* out, void* stream);
 

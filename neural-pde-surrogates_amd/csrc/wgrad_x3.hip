@@ -761,16 +761,57 @@ inline WxSplit wx_split(long ntiles, long base, const nps_wgrad_t& p) {
     return {splits, per, remap};
 }
 
+// The launch plan of nps_conv2d_wgrad_x3 / _set for *pp (host arithmetic only): the argument checks, the kernel and
+// its split-K schedule.  wgrad_x3_dispatch launches from it and nps_conv2d_wgrad_x3_plan reports it, so the tests
+// of the schedule read the launcher's own numbers.
+struct WxPlan {
+    int kernel;  // 0: wgrad_x3_kernel<KH, KW>, 1: wgrad1_wide_kernel, 2: wgrad2_wide_kernel
+    long ntiles, base;
+    int n_nt;
+    long splits;
+    int per, remap;
+    long grid() const { return base * splits; }
+};
+int wx_plan(const nps_wgrad_t* pp, WxPlan& pl) {
+    NPS_CHECK_ARG(pp != nullptr, "conv2d_wgrad_x3: null");
+    const nps_wgrad_t& p = *pp;
+    NPS_CHECK_ARG(p.a && p.x && p.g && p.B > 0 && p.Ha > 0 && p.Wa > 0 && p.M > 0 && p.Hx > 0 && p.Wx > 0 && p.N > 0,
+                  "conv2d_wgrad_x3: bad shape");
+    NPS_CHECK_ARG(p.dil == 1 && p.circ >= 0 && p.KH == p.KW && (p.KH == 1 || p.KH == 2 || p.KH == 3),
+                  "conv2d_wgrad_x3: kernel %dx%d dil %d unsupported (1x1 / 2x2 / 3x3, undilated)", p.KH, p.KW, p.dil);
+    NPS_CHECK_ARG((p.M & 3) == 0 && (p.N & 3) == 0 && (reinterpret_cast<size_t>(p.a) & 15) == 0 &&
+                      (reinterpret_cast<size_t>(p.x) & 15) == 0,
+                  "conv2d_wgrad_x3: channel counts %d, %d must be multiples of 4 (16-B pixel quads)", p.M, p.N);
+    int rows = 64;  // channel rows of one (m, n) tile
+    if (p.KH == 1 && p.pad_y == 0 && p.pad_x == 0 && p.circ == 0 && p.Ha == p.Hx && p.Wa == p.Wx) {
+        // dy and x on the same pixels (no padding / circular extension): the flat pixel range in 32-pixel tiles
+        pl.kernel = 1;
+        rows = W1_ROWS;
+        pl.ntiles = ((long)p.B * p.Ha * p.Wa + W1_TP - 1) / W1_TP;
+    } else if (p.KH == 2 && p.M > 64 && p.N > 64) {  // (the wide kernel needs M, N > 64 to beat the 64 x 64 tiles)
+        pl.kernel = 2;
+        rows = W2_ROWS;
+        pl.ntiles = (long)p.B * ((p.Ha + W2_TH - 1) / W2_TH) * ((p.Wa + W2_TW - 1) / W2_TW);
+    } else {
+        pl.kernel = 0;
+        pl.ntiles = (long)p.B * ((p.Ha + WX_TH - 1) / WX_TH) * ((p.Wa + WX_TW - 1) / WX_TW);
+    }
+    NPS_CHECK_ARG(pl.ntiles < (1L << 30), "conv2d_wgrad_x3: too many tiles");
+    pl.n_nt = (p.N + rows - 1) / rows;
+    pl.base = (long)((p.M + rows - 1) / rows) * pl.n_nt;
+    const WxSplit sp = wx_split(pl.ntiles, pl.base, p);
+    pl.splits = sp.splits;
+    pl.per = sp.per;
+    pl.remap = sp.remap;
+    NPS_CHECK_ARG(pl.grid() < (1L << 31), "conv2d_wgrad_x3: grid too large");
+    return 0;
+}
+
 template <int KH, int KW>
-int launch_wgrad_x3(const nps_wgrad_t& p, const float* ar, const float* xr, float* ws, hipStream_t s,
-                       int acc) {
-    const long tiles_x = (p.Wa + WX_TW - 1) / WX_TW, tiles_y = (p.Ha + WX_TH - 1) / WX_TH;
-    const long ntiles = (long)p.B * tiles_y * tiles_x;
-    NPS_CHECK_ARG(ntiles < (1L << 30), "conv2d_wgrad_x3: too many tiles");
-    const int n_mt = (p.M + 63) / 64, n_nt = (p.N + 63) / 64;
-    const long base = (long)n_mt * n_nt;
-    const auto [splits, per, remap] = wx_split(ntiles, base, p);
-    NPS_CHECK_ARG(base * splits < (1L << 31), "conv2d_wgrad_x3: grid too large");
+int launch_wgrad_x3(const nps_wgrad_t& p, const WxPlan& pl, const float* ar, const float* xr, float* ws,
+                    hipStream_t s, int acc) {
+    const long ntiles = pl.ntiles, base = pl.base, splits = pl.splits;
+    const int n_nt = pl.n_nt, per = pl.per, remap = pl.remap;
     const size_t lds = wx_lds_bytes(KH);
     static bool attr_set = false;
     if (!attr_set) {
@@ -795,15 +836,11 @@ int launch_wgrad_x3(const nps_wgrad_t& p, const float* ar, const float* xr, floa
 }
 
 // 1x1 weight gradient on wgrad1_wide_kernel (dy and x on the same pixels: no padding / circular extension)
-int launch_wgrad1_wide(const nps_wgrad_t& p, const float* ar, const float* xr, float* ws, hipStream_t s,
-                       int acc) {
+int launch_wgrad1_wide(const nps_wgrad_t& p, const WxPlan& pl, const float* ar, const float* xr, float* ws,
+                       hipStream_t s, int acc) {
     const long npix = (long)p.B * p.Ha * p.Wa;
-    const long ntiles = (npix + W1_TP - 1) / W1_TP;
-    NPS_CHECK_ARG(ntiles < (1L << 30), "conv2d_wgrad_x3 (1x1): too many tiles");
-    const int n_mt = (p.M + W1_ROWS - 1) / W1_ROWS, n_nt = (p.N + W1_ROWS - 1) / W1_ROWS;
-    const long base = (long)n_mt * n_nt;
-    const auto [splits, per, remap] = wx_split(ntiles, base, p);
-    NPS_CHECK_ARG(base * splits < (1L << 31), "conv2d_wgrad_x3 (1x1): grid too large");
+    const long ntiles = pl.ntiles, base = pl.base, splits = pl.splits;
+    const int n_nt = pl.n_nt, per = pl.per, remap = pl.remap;
     static bool attr_set = false;
     if (!attr_set) {
         (void)hipFuncSetAttribute((const void*)wgrad1_wide_kernel, hipFuncAttributeMaxDynamicSharedMemorySize,
@@ -826,15 +863,10 @@ int launch_wgrad1_wide(const nps_wgrad_t& p, const float* ar, const float* xr, f
 }
 
 // 2x2 weight gradient on wgrad2_wide_kernel (128 x 128 work-group tiles)
-int launch_wgrad2_wide(const nps_wgrad_t& p, const float* ar, const float* xr, float* ws, hipStream_t s,
-                       int acc) {
-    const long tiles_x = (p.Wa + W2_TW - 1) / W2_TW, tiles_y = (p.Ha + W2_TH - 1) / W2_TH;
-    const long ntiles = (long)p.B * tiles_y * tiles_x;
-    NPS_CHECK_ARG(ntiles < (1L << 30), "conv2d_wgrad_x3 (2x2): too many tiles");
-    const int n_mt = (p.M + W2_ROWS - 1) / W2_ROWS, n_nt = (p.N + W2_ROWS - 1) / W2_ROWS;
-    const long base = (long)n_mt * n_nt;
-    const auto [splits, per, remap] = wx_split(ntiles, base, p);
-    NPS_CHECK_ARG(base * splits < (1L << 31), "conv2d_wgrad_x3 (2x2): grid too large");
+int launch_wgrad2_wide(const nps_wgrad_t& p, const WxPlan& pl, const float* ar, const float* xr, float* ws,
+                       hipStream_t s, int acc) {
+    const long ntiles = pl.ntiles, base = pl.base, splits = pl.splits;
+    const int n_nt = pl.n_nt, per = pl.per, remap = pl.remap;
     static bool attr_set = false;
     if (!attr_set) {
         (void)hipFuncSetAttribute((const void*)wgrad2_wide_kernel, hipFuncAttributeMaxDynamicSharedMemorySize,
@@ -865,28 +897,35 @@ namespace {
 int wgrad_x3_dispatch(const nps_wgrad_t* pp, const float* a_range, const float* x_range, float* ws, void* stream,
                       int acc) {
     NPS_CHECK_ARG(pp != nullptr && a_range != nullptr && x_range != nullptr && ws != nullptr, "conv2d_wgrad_x3: null");
+    WxPlan pl;
+    if (const int rc = wx_plan(pp, pl); rc != 0) return rc;
     const nps_wgrad_t& p = *pp;
-    NPS_CHECK_ARG(p.a && p.x && p.g && p.B > 0 && p.Ha > 0 && p.Wa > 0 && p.M > 0 && p.Hx > 0 && p.Wx > 0 && p.N > 0,
-                  "conv2d_wgrad_x3: bad shape");
-    NPS_CHECK_ARG(p.dil == 1 && p.circ >= 0 && p.KH == p.KW && (p.KH == 1 || p.KH == 2 || p.KH == 3),
-                  "conv2d_wgrad_x3: kernel %dx%d dil %d unsupported (1x1 / 2x2 / 3x3, undilated)", p.KH, p.KW, p.dil);
-    NPS_CHECK_ARG((p.M & 3) == 0 && (p.N & 3) == 0 && (reinterpret_cast<size_t>(p.a) & 15) == 0 &&
-                      (reinterpret_cast<size_t>(p.x) & 15) == 0,
-                  "conv2d_wgrad_x3: channel counts %d, %d must be multiples of 4 (16-B pixel quads)", p.M, p.N);
     hipStream_t s = (hipStream_t)stream;
+    if (pl.kernel == 1) return launch_wgrad1_wide(p, pl, a_range, x_range, ws, s, acc);
+    if (pl.kernel == 2) return launch_wgrad2_wide(p, pl, a_range, x_range, ws, s, acc);
     switch (p.KH) {
-        case 1:
-            if (p.pad_y == 0 && p.pad_x == 0 && p.circ == 0 && p.Ha == p.Hx && p.Wa == p.Wx)
-                return launch_wgrad1_wide(p, a_range, x_range, ws, s, acc);
-            return launch_wgrad_x3<1, 1>(p, a_range, x_range, ws, s, acc);
-        case 2:
-            // (the wide kernel needs M, N > 64 to beat the 64 x 64 tiles)
-            if (p.M > 64 && p.N > 64) return launch_wgrad2_wide(p, a_range, x_range, ws, s, acc);
-            return launch_wgrad_x3<2, 2>(p, a_range, x_range, ws, s, acc);
-        default: return launch_wgrad_x3<3, 3>(p, a_range, x_range, ws, s, acc);
+        case 1: return launch_wgrad_x3<1, 1>(p, pl, a_range, x_range, ws, s, acc);
+        case 2: return launch_wgrad_x3<2, 2>(p, pl, a_range, x_range, ws, s, acc);
+        default: return launch_wgrad_x3<3, 3>(p, pl, a_range, x_range, ws, s, acc);
     }
 }
 }  // namespace
+
+// Test hook: the plan the two entry points below launch from (no range tags, workspace or stream: nothing launches)
+extern "C" int nps_conv2d_wgrad_x3_plan(const nps_wgrad_t* pp, int out[8]) {
+    NPS_CHECK_ARG(out != nullptr, "conv2d_wgrad_x3_plan: null");
+    WxPlan pl;
+    if (const int rc = wx_plan(pp, pl); rc != 0) return rc;
+    out[0] = pl.kernel;
+    out[1] = (int)pl.ntiles;
+    out[2] = (int)pl.base;
+    out[3] = pl.n_nt;
+    out[4] = (int)pl.splits;
+    out[5] = pl.per;
+    out[6] = pl.remap;
+    out[7] = (int)pl.grid();
+    return 0;
+}
 
 extern "C" int nps_conv2d_wgrad_x3(const nps_wgrad_t* pp, const float* a_range, const float* x_range, float* ws,
                                    void* stream) {

@@ -117,8 +117,10 @@ WGRAD_X3_CASES = [
     (2, 192, 768, 2, 0, 0, 33, 31, 1.0, 1.0),
     (1, 100, 136, 2, 1, 0, 19, 21, 1e-4, 1e3),
     (2, 132, 80, 2, 0, 1, 20, 24, 1.0, 1.0),
-    # N tails of <= 8 channels past the 64-channel tiles on wgrad_tail_kernel (the 388 / 196-channel U-Net frames):
-    # padding, circular extension, 2x2 with an 8-channel tail, range
+    # N tails of <= 8 channels past the 64-channel tiles (the 388 / 196-channel U-Net frames): padding, circular
+    # extension, 2x2 with an 8-channel tail, range.  All four run wgrad_x3_kernel<KH, KW> (nps_conv2d_wgrad_x3_plan:
+    # kernel 0 — the 2x2 one has M = 48 <= 64), the tail as one more, mostly empty, 64-channel n-tile: base 21, 2, 3, 2
+    # (m, n) tiles in the plain tile-fastest order
     (2, 192, 388, 3, 1, 0, 29, 31, 1.0, 1.0),
     (2, 64, 68, 3, 0, 1, 22, 26, 1e-4, 1e3),
     (1, 48, 136, 2, 1, 0, 18, 21, 1.0, 1.0),
