@@ -461,11 +461,20 @@ int nps_conv1x1_bf16(const nps_conv2d_t* a, void* stream);
  * zero-padded to Cp channels; vb[B][H][W][K+S] = [cond broadcast | sc]. */
 int nps_pack_grid_input(const float* u, const float* pos, const float* cond, const float* sc, float* xin,
                         float* vb, int B, int CT, int H, int W, int K, int S, int Cp, void* stream);
+/* The same packing on a grid of any dimension, over N = the product of the spatial extents (L, H*W, D*H*W) flat
+ * pixels: u planar [B][CT][N], pos [B][N][P], cond [B][K], sc [B][S][N] ->
+ * xin[B][N][Cp] = [u | pos(P) | cond(K) broadcast | sc(S) | 0-pad], vb[B][N][K+S] = [cond broadcast | sc] (vb may be
+ * NULL when K + S == 0).  P, the number of position channels, is the grid's dimension: 1, 2 or 3 (anything else is
+ * an error); Cp % 4 == 0, Cp >= CT + P + K + S, 260 * Cp bytes of LDS <= 64 KiB.  nps_pack_grid_input is this with
+ * N = H * W, P = 2. */
+int nps_pack_grid_input_nd(const float* u, const float* pos, const float* cond, const float* sc, float* xin,
+                           float* vb, int B, int CT, int N, int P, int K, int S, int Cp, void* stream);
 /* TimeConvDense conv1d chain + add_delta + tanh + spatial-cond mask
  * (dec_grid.py:126-146, :8-31; activation_wrapper.py:34-35).
  * pre: [B][num_c*3*tw][H][W] (planar pre_decoder output), u: model input
  * (B,num_c,tw,H,W); out: (B,num_c,tw,H,W).  dtcum[tw] = fp32 cumsum(dt).
- * mask: (B,S,H,W) channel `mask_ch` or NULL. */
+ * mask: (B,S,H,W) channel `mask_ch` or NULL.  The chain is per pixel and the kernels index by H * W only: a 1-D or
+ * 3-D grid passes its flat pixel count as H = 1, W = N (nps_timeconv_decode_bwd likewise). */
 int nps_timeconv_decode(const float* pre, const float* u, const float* w1, const float* b1, const float* w2,
                         const float* b2, const float* dtcum, const float* mask, int mask_S, int mask_ch,
                         float* out, int B, int num_c, int tw, int H, int W, int act_tanh, void* stream);

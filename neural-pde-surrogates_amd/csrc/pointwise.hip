@@ -23,14 +23,16 @@ namespace {
 
 // ---------------------------------------------------------------- encoder input
 // One block = 64 pixels of one sample; channels staged through LDS so both the
-// planar reads of u and the NHWC writes are coalesced.
+// planar reads of u and the NHWC writes are coalesced.  A pixel is an index into the flattened
+// spatial axes (N = L, H*W or D*H*W); P = the number of position channels (the grid's dimension).
+template <int P>
 __global__ void pack_grid_kernel(const float* __restrict__ u, const float* __restrict__ pos,
                                  const float* __restrict__ cond, const float* __restrict__ sc, float* __restrict__ xin,
-                                 float* __restrict__ vb, int CT, int HW, int K, int S, int Cp) {
+                                 float* __restrict__ vb, int CT, int N, int K, int S, int Cp) {
     extern __shared__ float tile[];  // [Cp][65]
     const int b = blockIdx.y;
     const int p0 = blockIdx.x * 64;
-    const int np = min(64, HW - p0);
+    const int np = min(64, N - p0);
     const int KS = K + S;
     for (int i = threadIdx.x; i < Cp * 64; i += blockDim.x) {
         const int ch = i / 64, p = i % 64;
@@ -38,25 +40,25 @@ __global__ void pack_grid_kernel(const float* __restrict__ u, const float* __res
         if (p < np) {
             const int pix = p0 + p;
             if (ch < CT)
-                v = u[((size_t)b * CT + ch) * HW + pix];
-            else if (ch < CT + 2)
-                v = pos[((size_t)b * HW + pix) * 2 + (ch - CT)];
-            else if (ch < CT + 2 + K)
-                v = cond[b * K + (ch - CT - 2)];
-            else if (ch < CT + 2 + KS)
-                v = sc[((size_t)b * S + (ch - CT - 2 - K)) * HW + pix];
+                v = u[((size_t)b * CT + ch) * N + pix];
+            else if (ch < CT + P)
+                v = pos[((size_t)b * N + pix) * P + (ch - CT)];
+            else if (ch < CT + P + K)
+                v = cond[b * K + (ch - CT - P)];
+            else if (ch < CT + P + KS)
+                v = sc[((size_t)b * S + (ch - CT - P - K)) * N + pix];
         }
         tile[ch * 65 + p] = v;
     }
     __syncthreads();
     for (int i = threadIdx.x; i < np * Cp; i += blockDim.x) {
         const int p = i / Cp, ch = i % Cp;
-        xin[((size_t)b * HW + p0 + p) * Cp + ch] = tile[ch * 65 + p];
+        xin[((size_t)b * N + p0 + p) * Cp + ch] = tile[ch * 65 + p];
     }
     if (vb != nullptr) {
         for (int i = threadIdx.x; i < np * KS; i += blockDim.x) {
             const int p = i / KS, ch = i % KS;
-            vb[((size_t)b * HW + p0 + p) * KS + ch] = tile[(CT + 2 + ch) * 65 + p];
+            vb[((size_t)b * N + p0 + p) * KS + ch] = tile[(CT + P + ch) * 65 + p];
         }
     }
 }
@@ -777,6 +779,32 @@ __global__ void volume_rescale_bwd_kernel(const float* __restrict__ g,
 
 }  // namespace
 
+extern "C" int nps_pack_grid_input_nd(const float* u, const float* pos, const float* cond, const float* sc,
+                                      float* xin, float* vb, int B, int CT, int N, int P, int K, int S, int Cp,
+                                      void* stream) {
+    NPS_CHECK_ARG(P >= 1 && P <= 3, "pack_grid_input: P=%d position channels (a 1-D, 2-D or 3-D grid has 1, 2 or 3)",
+                  P);
+    NPS_CHECK_ARG(u && pos && xin && B > 0 && B <= 65535 && CT > 0 && N > 0 && K >= 0 && S >= 0 && Cp % 4 == 0 &&
+                      Cp >= CT + P + K + S,
+                  "pack_grid_input: bad args");
+    NPS_CHECK_ARG(N <= 0x7fffffff - 64, "pack_grid_input: N=%d pixels: the block index would overflow", N);
+    NPS_CHECK_ARG((K == 0 || cond) && (S == 0 || sc), "pack_grid_input: missing cond/spatial cond");
+    NPS_CHECK_ARG(K + S == 0 || vb, "pack_grid_input: missing vb");
+    const size_t lds = sizeof(float) * Cp * 65;
+    NPS_CHECK_ARG(lds <= 64 * 1024, "pack_grid_input: Cp=%d too large", Cp);
+    const dim3 grid((N + 63) / 64, B);
+    float* vbp = (K + S) ? vb : nullptr;
+    hipStream_t st = (hipStream_t)stream;
+    if (P == 1)
+        pack_grid_kernel<1><<<grid, 256, lds, st>>>(u, pos, cond, sc, xin, vbp, CT, N, K, S, Cp);
+    else if (P == 2)
+        pack_grid_kernel<2><<<grid, 256, lds, st>>>(u, pos, cond, sc, xin, vbp, CT, N, K, S, Cp);
+    else
+        pack_grid_kernel<3><<<grid, 256, lds, st>>>(u, pos, cond, sc, xin, vbp, CT, N, K, S, Cp);
+    NPS_CHECK_LAUNCH("pack_grid_input");
+    return 0;
+}
+
 extern "C" int nps_pack_grid_input(const float* u, const float* pos, const float* cond, const float* sc, float* xin,
                                    float* vb, int B, int CT, int H, int W, int K, int S, int Cp, void* stream) {
     NPS_CHECK_ARG(u && pos && xin && B > 0 && CT > 0 && H > 0 && W > 0 && K >= 0 && S >= 0 && Cp >= CT + 2 + K + S,
@@ -785,9 +813,9 @@ extern "C" int nps_pack_grid_input(const float* u, const float* pos, const float
     const size_t lds = sizeof(float) * Cp * 65;
     NPS_CHECK_ARG(lds <= 64 * 1024, "pack_grid_input: Cp=%d too large", Cp);
     const int HW = H * W;
-    pack_grid_kernel<<<dim3((HW + 63) / 64, B), 256, lds, (hipStream_t)stream>>>(u, pos, cond, sc, xin,
-                                                                                 (K + S) ? vb : nullptr, CT, HW, K, S,
-                                                                                 Cp);
+    pack_grid_kernel<2><<<dim3((HW + 63) / 64, B), 256, lds, (hipStream_t)stream>>>(u, pos, cond, sc, xin,
+                                                                                    (K + S) ? vb : nullptr, CT, HW, K,
+                                                                                    S, Cp);
     NPS_CHECK_LAUNCH("pack_grid_input");
     return 0;
 }

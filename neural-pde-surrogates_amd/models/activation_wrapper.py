@@ -34,6 +34,13 @@ def activation_wrapper(model_class: str, activation_final: nn.Module, enforce_sp
     def new_forward(self, *a, **b):
         if not isinstance(self, models.EncProcDec) or not isinstance(activation_final, nn.Tanh):
             raise NotImplementedError("activation_wrapper: the fused MI355X path wraps EncProcDec with Tanh")
+        nd = self.num_spatial_dims
+        if nd != 2 and enforce_spatial_cond:
+            # activation_wrapper.py:28 repeats the mask as 'b x y -> b c tw x y': the reference cannot run it either
+            raise NotImplementedError(f"activation_wrapper: enforce_spatial_cond is defined on 2-D grids only, not "
+                                      f"{nd}-D (spatial_cond as input channels works in every dimension)")
+        if nd != 2 and approx_volume_preserve:
+            raise ValueError(f"{nd} spatial dims not supported for approx volume preserve")  # :52, :78, :100
         x = b["x"] if "x" in b else a[0]
         fwd_kw = dict(b)
         fwd_kw.pop("x", None)

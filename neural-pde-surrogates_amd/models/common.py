@@ -123,6 +123,10 @@ class Conv2d(_PackedMixin, nn.Conv2d):
         return ops.conv2d(srcs, frame_hw, pk, self.bias, self.out_channels, KH, KW,
                           stride=s, dil=d, pad=lo, pad_bottom=hi, circ=circ, **kw)
 
+    def run_ad(self, x):
+        """Differentiable form on an NHWC tensor (the method Conv1d / Conv3d give their pointwise views)."""
+        return ad.conv2d(self, x)
+
     def forward(self, x):
         if use_autograd(self):
             return ad.to_nchw(ad.conv2d(self, ad.to_nhwc(x)))
@@ -340,6 +344,30 @@ class Conv1d(_PackedMixin, nn.Conv1d):
         self._check()
         return ad.Conv2dFn.apply(self.geometry(), x, self.weight.reshape(self.out_channels, self.in_channels, 1, 1),
                                  self.bias)
+
+
+def flat_frame(spatial):
+    """The (rows, row length) arrangement of a grid's flat pixels that the per-pixel NHWC launches (pointwise convs,
+    spectral layers) take: (1, L), (H, W) or (D*H, W).  Channels-last (B, N, C) tensors view to (B, rows, row, C)."""
+    spatial = tuple(int(s) for s in spatial)
+    if len(spatial) == 1:
+        return 1, spatial[0]
+    if len(spatial) == 2:
+        return spatial
+    if len(spatial) == 3:
+        return spatial[0] * spatial[1], spatial[2]
+    raise NotImplementedError(f"grids have 1 to 3 spatial axes, got {len(spatial)}")
+
+
+def run_pointwise(conv, x, **kw):
+    """conv.run on the one source x (B, rows, row, C) of a pointwise conv.  A Conv1d's 1 x L image folds into
+    32-point rows when L % 32 == 0 (as FNO_Layer.run folds its `w`: full conv tiles instead of 1/8 .. 1/32 used);
+    the output comes back in x's arrangement (planar with out_nchw=True, where the fold changes nothing)."""
+    B, R, L, _ = x.shape
+    if not (isinstance(conv, Conv1d) and R == 1 and L % 32 == 0 and L > 32):
+        return conv.run([ops.Src(x)], (R, L), **kw)
+    y = conv.run([ops.Src(ops.pixel_view(x, (B, L // 32, 32, x.shape[3])))], (L // 32, 32), **kw)
+    return y.view(B, -1, 1, L) if kw.get("out_nchw") else ops.pixel_view(y, (B, 1, L, y.shape[3]))
 
 
 def get_conv_with_right_spatial_dim(spatial_dim, **kwargs):

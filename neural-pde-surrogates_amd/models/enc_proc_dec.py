@@ -4,7 +4,10 @@
 (enc_proc_dec.py:14-38), against this package.  The forward packs
 [u | pos | cond | spatial_cond] into one NHWC tensor with one HIP kernel and
 then runs encoder -> processors -> decoder as fused HIP launches on NHWC
-tensors; only the final (B, c, tw, H, W) output leaves that layout.
+tensors; only the final (B, c, tw, H, W) output leaves that layout.  1-D and
+3-D grids take the same route over their flat pixels: the pack, the encoder,
+the FNO layers and the decoder are per pixel, and the 3-D U-Net / U-FNO walk
+the NDHWC view of the same buffers.
 """
 from argparse import Namespace
 from typing import Union
@@ -13,6 +16,10 @@ import torch
 from torch import nn
 
 from models.base import ModelInterface
+from models.common import flat_frame
+from models.enc_proc_dec_components.proc_fno import FNO
+from models.enc_proc_dec_components.proc_ufno import UFNO
+from models.enc_proc_dec_components.proc_unet_modern import UNetModern
 from nps_hip import ops
 from nps_hip import autograd as ad
 from pdes import PDE
@@ -95,8 +102,13 @@ class EncProcDec(ModelInterface):
         cond, bc, pos, t_cond, spatial_cond = map(check_none, (cond, bc, pos, t_cond, spatial_cond))
         if self.data_structure != "grid":
             raise NotImplementedError("graph data_structure is deprecated in the reference and not built")
-        if self.num_spatial_dims != 2:
-            raise NotImplementedError("EncProcDec: 2-D grids only on the MI355X path")
+        nd = self.num_spatial_dims
+        if x.dim() != 3 + nd:
+            raise ValueError(f"EncProcDec(num_spatial_dims={nd}): x must be (B, c, tw, *spatial) with {nd} spatial "
+                             f"axes, got {tuple(x.shape)}")
+        self._check_processors()
+        if mask_channel is not None and nd != 2:
+            raise NotImplementedError("enforce_spatial_cond: 2-D grids only")
         if not x.is_cuda:
             raise RuntimeError("nps: the model runs on the MI355X; move inputs to the GPU")
         u = x.contiguous()
@@ -105,21 +117,59 @@ class EncProcDec(ModelInterface):
         n_in = self.encoder.n_in
         Cp = ((n_in + 3) // 4) * 4
         xin, vb = ops.pack_grid_input(u, pos.float().contiguous(), variables, sc, Cp)
+        if nd != 2:
+            # off the 2-D grid the encoder, the FNO layers and the decoder run per pixel on the (B, 1, L, C) /
+            # (B, D*H, W, C) view of the flat pixels (common.flat_frame)
+            frame = (u.shape[0],) + flat_frame(u.shape[3:])
+            xin = xin.view(frame + (Cp,))
+            vb = vb.view(frame + (vb.shape[-1],)) if vb is not None else None
         mask = sc if mask_channel is not None else None
         if torch.is_grad_enabled() and any(p.requires_grad for p in self.parameters()):
             # training: the same kernels unfused, each with its HIP backward (nps_hip.autograd)
             h = self.encoder.run_packed_ad(xin)
             for i, p in enumerate(self.processor):
-                h_next = p.run_ad(h, vb)
+                h_next = self._process(p, h, vb, u.shape[3:], True)
                 h = ad.add_at(h_next, h) if (self.processor_residual and i > 0) else h_next
             return self.decoder.run_ad(h, u, final_tanh=final_tanh, mask=mask, mask_ch=mask_channel or 0)
-        h = self.encoder.run_packed(xin)
+        # (off the 2-D grid only a U-Net's first norm reads the encoder output's moments)
+        h = self.encoder.run_packed(xin, carry_stats=None if nd == 2 else
+                                    (ops.CARRY3D and not isinstance(self.processor[0], FNO)))
         for i, p in enumerate(self.processor):
-            h_next = p.run(h, vb)
+            h_next = self._process(p, h, vb, u.shape[3:], False)
             if self.processor_residual and i > 0:
                 h_next = h_next + h
             h = h_next
         return self.decoder.run(h, u, final_tanh=final_tanh, mask=mask, mask_ch=mask_channel or 0)
+
+    def _check_processors(self):
+        """Off the 2-D grid: FNO in 1-D; FNO, U-FNO and U-Net in 3-D.  Anything else has no HIP path there and is
+        refused before any launch."""
+        nd = self.num_spatial_dims
+        if nd == 2:
+            return
+        if nd not in (1, 3):
+            raise NotImplementedError(f"EncProcDec: grids have 1 to 3 spatial axes, got num_spatial_dims={nd}")
+        for p in self.processor:
+            if not (isinstance(p, FNO) or (nd == 3 and isinstance(p, (UFNO, UNetModern)))):
+                raise NotImplementedError(f"EncProcDec: the processor {type(p).__name__} has no {nd}-D HIP path "
+                                          f"(1-D: FNO; 3-D: FNO, UFNO, UNetModern)")
+            if nd == 1:
+                for layer in p.fno_layers:
+                    layer._check_1d()  # fno_kernel_size > 1
+
+    def _process(self, p, h, vb, spatial, train):
+        """One processor on h, vb in the flat-pixel frame of the grid, in the form it takes them."""
+        nd = len(spatial)
+        if nd == 2:
+            return p.run_ad(h, vb) if train else p.run(h, vb)
+        if isinstance(p, FNO):
+            kw = dict(D=spatial[0]) if nd == 3 else {}
+            return p.run_ad(h, vb, **kw) if train else p.run(h, vb, **kw)
+        # the 3-D U-Net / U-FNO walk NDHWC volumes
+        ndhwc = lambda t: ops.pixel_view(t, (t.shape[0],) + tuple(spatial) + (t.shape[3],))  # noqa: E731
+        h5, vb5 = ndhwc(h), ndhwc(vb) if vb is not None else None
+        y = p.run_ad3d(h5, vb5) if train else p.run3d(h5, vb5)
+        return ops.pixel_view(y, tuple(h.shape[:3]) + (y.shape[4],))
 
     def forward(self, x, cond=None, bc=None, pos=None, t_cond=None, spatial_cond=None):
         return self.forward_fused(x, cond=cond, bc=bc, pos=pos, t_cond=t_cond, spatial_cond=spatial_cond)

@@ -11,7 +11,8 @@ import numpy as np
 import torch
 from torch import nn
 
-from models.common import get_conv_with_right_spatial_dim, Swish, activation_code, use_autograd
+from models.common import (get_conv_with_right_spatial_dim, Swish, activation_code, use_autograd, flat_frame,
+                           run_pointwise)
 from nps_hip import ops
 from nps_hip import autograd as ad
 from pdes import PDE
@@ -59,13 +60,13 @@ class TimeConvDense(nn.Module):
         return self._dt_tab
 
     def run(self, h, u, final_tanh=False, mask=None, mask_ch=0):
-        """h: (B,H,W,hidden) NHWC; u: model input (B,c,tw,H,W).  Returns (B,c,tw,H,W)."""
+        """h: (B,H,W,hidden) NHWC — a 1-D / 3-D grid's flat pixels as the (B, 1, L, hidden) / (B, D*H, W, hidden)
+        view (common.flat_frame); u: model input (B,c,tw,*spatial).  Returns (B,c,tw,*spatial)."""
         if self.dec_delta_mode != 'per_step':
             raise NotImplementedError("TimeConvDense: dec_delta_mode='per_step' only on the MI355X path")
         if activation_code(self.decoder[1]) != ops.GELU:
             raise NotImplementedError("TimeConvDense: GELU activation only")
-        H, W = h.shape[1:3]
-        pre = self.pre_decoder.run([ops.Src(h)], (H, W), out_nchw=True)
+        pre = run_pointwise(self.pre_decoder, h, out_nchw=True)
         c1, c2 = self.decoder[0], self.decoder[2]
         return ops.timeconv_decode(pre, u.contiguous(), c1.weight.detach().contiguous(), c1.bias.detach(),
                                    c2.weight.detach().contiguous(), c2.bias.detach(), self._dtcum(h.device), mask,
@@ -77,13 +78,17 @@ class TimeConvDense(nn.Module):
             raise NotImplementedError("TimeConvDense: dec_delta_mode='per_step' only on the MI355X path")
         if activation_code(self.decoder[1]) != ops.GELU:
             raise NotImplementedError("TimeConvDense: GELU activation only")
-        pre = ad.to_nchw(ad.conv2d(self.pre_decoder, h))
+        pre = ad.to_nchw(self.pre_decoder.run_ad(h))
         c1, c2 = self.decoder[0], self.decoder[2]
         return ad.TimeConvDecodeFn.apply((mask_ch, bool(final_tanh), self.num_c, self.time_window), pre,
                                          u.contiguous(), c1.weight, c1.bias, c2.weight, c2.bias,
                                          self._dtcum(h.device), mask)
 
     def forward(self, h: torch.Tensor, u: torch.Tensor, **kwargs):
+        """h (B, hidden, *spatial), u (B, c, tw, *spatial) on a 1-D, 2-D or 3-D grid -> (B, c, tw, *spatial)."""
+        if tuple(h.shape[2:]) != tuple(u.shape[3:]) or h.shape[0] != u.shape[0]:
+            raise RuntimeError(f"TimeConvDense: h {tuple(h.shape)} and u {tuple(u.shape)} lie on different grids")
+        h = h.reshape((h.shape[0], h.shape[1]) + flat_frame(u.shape[3:]))
         if use_autograd(self):
             return self.run_ad(ad.to_nhwc(h), u)
         return self.run(ops.nchw_to_nhwc(h), u)

@@ -126,6 +126,7 @@ _SIGS = {
     "nps_spectral_idft_h": (_i, [_vp, _vp, _i, _i, _i, _i, _i, _vp]),
     "nps_spectral_idft_w": (_i, [_vp, _vp, _i, _i, _i, _i, _i, _i, _vp, _i, _vp, _vp]),
     "nps_pack_grid_input": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _i, _vp]),
+    "nps_pack_grid_input_nd": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _i, _vp]),
     "nps_timeconv_decode": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _vp, _i, _i, _i, _i, _i, _i,
                                  _vp]),
     "nps_plane_sums": (_i, [_vp, _l, _i, _i, _vp, _vp]),

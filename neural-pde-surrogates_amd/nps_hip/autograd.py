@@ -1089,7 +1089,7 @@ class TimeConvDecodeFn(torch.autograd.Function):
         pre, u, w1, b1, w2, b2, dtcum, mask = ctx.saved_tensors
         mask = mask if ctx.has_mask else None
         gout = _c(gout)
-        B, _, _, H, W = u.shape
+        B, H, W = u.shape[0], 1, ops.grid_pixels(u)  # per pixel: a grid of any dimension as its flat pixels
         ka, kb = w1.shape[2], w2.shape[2]
         C2 = 2 * num_c
         nparams = C2 * num_c * ka + C2 + num_c * C2 * kb + num_c

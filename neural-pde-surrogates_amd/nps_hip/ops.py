@@ -362,6 +362,15 @@ def attach_stats(t: torch.Tensor, st: torch.Tensor) -> torch.Tensor:
     return t
 
 
+def pixel_view(t: torch.Tensor, shape) -> torch.Tensor:
+    """t.view(shape) of a channels-last tensor whose pixels are only arranged differently ((B, D*H, W, C) <->
+    (B, D, H, W, C), (B, 1, L, C) <-> (B, L/32, 32, C)): the view keeps t's range tag and its GroupNorm(1) moments,
+    which are a bound on, and sums over, the same elements."""
+    v = share_tag(t.view(shape), t)
+    st = stats_of(t)
+    return attach_stats(v, st) if st is not None else v
+
+
 def drop_stats(t: torch.Tensor):
     if getattr(t, "_nps_stats", None) is not None:
         t._nps_stats = None
@@ -1554,24 +1563,45 @@ def nhwc_to_nchw(x: torch.Tensor) -> torch.Tensor:
     return share_tag(out, x)
 
 
+def grid_pixels(u: torch.Tensor) -> int:
+    """N, the flat pixel count of a model tensor (B, c, tw, *spatial) on a 1-D, 2-D or 3-D grid."""
+    if not 4 <= u.dim() <= 6:
+        raise RuntimeError(f"nps_hip: (B, c, tw, *spatial) with 1 to 3 spatial axes, got {tuple(u.shape)}")
+    return math.prod(u.shape[3:])
+
+
 def pack_grid_input(u, pos, cond, sc, Cp):
-    """-> (xin (B,H,W,Cp), vb (B,H,W,K+S) or None)."""
-    B, c, tw, H, W = u.shape
+    """u (B, c, tw, *spatial) on a 1-D, 2-D or 3-D grid, pos (B, *spatial, P) with P = the grid's dimension (1-D: also
+    (B, L)), cond (B, K) or None, sc (B, S, *spatial) or None -> (xin (B, N, Cp), vb (B, N, K+S) or None) over the
+    N = prod(spatial) flat pixels; on a 2-D grid the (B, H, W, .) tensors."""
+    N = grid_pixels(u)
+    B, c, tw = u.shape[:3]
+    spatial = tuple(u.shape[3:])
+    if len(spatial) == 1 and pos.dim() == 2:
+        pos = pos.unsqueeze(-1)  # enc_grid.py:43-44
+    P = pos.shape[-1]
+    if tuple(pos.shape) != (B,) + spatial + (P,):
+        raise RuntimeError(f"pack_grid_input: pos {tuple(pos.shape)} does not lie on u's grid {spatial}")
+    if sc is not None and tuple(sc.shape[2:]) != spatial:
+        raise RuntimeError(f"pack_grid_input: spatial cond {tuple(sc.shape)} does not lie on u's grid {spatial}")
     K = 0 if cond is None else cond.shape[1]
     S = 0 if sc is None else sc.shape[1]
-    xin = torch.empty((B, H, W, Cp), dtype=torch.float32, device=u.device)
-    vb = torch.empty((B, H, W, K + S), dtype=torch.float32, device=u.device) if K + S > 0 else None
-    check(lib.nps_pack_grid_input(ptr(u), ptr(pos), ptr(cond), ptr(sc), ptr(xin), ptr(vb), B, c * tw, H, W, K, S, Cp,
-                                  stream_ptr()), "pack_grid_input")
+    shape = (B,) + spatial if len(spatial) == 2 else (B, N)
+    xin = torch.empty(shape + (Cp,), dtype=torch.float32, device=u.device)
+    vb = torch.empty(shape + (K + S,), dtype=torch.float32, device=u.device) if K + S > 0 else None
+    check(lib.nps_pack_grid_input_nd(ptr(u), ptr(pos), ptr(cond), ptr(sc), ptr(xin), ptr(vb), B, c * tw, N, P, K, S,
+                                     Cp, stream_ptr()), "pack_grid_input")
     return xin, vb
 
 
 def timeconv_decode(pre, u, w1, b1, w2, b2, dtcum, mask, mask_ch, act_tanh, num_c, tw):
-    B, _, _, H, W = u.shape
-    out = torch.empty((B, num_c, tw, H, W), dtype=torch.float32, device=u.device)
+    """pre: the planar (B, 3*num_c*tw, N) pre-decoder output in any view; u, the model input (B, c, tw, *spatial) ->
+    (B, num_c, tw, *spatial).  The chain is per pixel: the kernels take the flat pixel count as H * W."""
+    B, N = u.shape[0], grid_pixels(u)
+    out = torch.empty((B, num_c, tw) + tuple(u.shape[3:]), dtype=torch.float32, device=u.device)
     S = 0 if mask is None else mask.shape[1]
     check(lib.nps_timeconv_decode(ptr(pre), ptr(u), ptr(w1), ptr(b1), ptr(w2), ptr(b2), ptr(dtcum), ptr(mask), S,
-                                  mask_ch, ptr(out), B, num_c, tw, H, W, 1 if act_tanh else 0, stream_ptr()),
+                                  mask_ch, ptr(out), B, num_c, tw, 1, N, 1 if act_tanh else 0, stream_ptr()),
           "timeconv_decode")
     return out
 
