@@ -764,6 +764,54 @@ size_t nps_attn_bwd_ws_floats(int B, int N, int heads, int dk);
 int nps_attn_bwd(const float* qkv, const float* lse, const float* dout, float* dqkv, float* ws, int B, int N,
                  int heads, int dk, float scale, void* stream);
 
+/* ---- 1-D U-Net convs (fp32, exact-fp32 MFMA v_mfma_f32_32x32x2_f32): k-tap Conv1d along L ----
+ * Activations are channels-last [B][L][C] fp32, contiguous.  The input is a virtual frame of Lc positions and Cin
+ * channels: the channel concatenation of up to NPS_MAX_SRC sources, source i placed at frame position off (crop_Nd:
+ * off > 0 zero-pads, off < 0 crops; a source shorter than the frame reads as zero outside itself).  Everything
+ * outside [0, Lc) of the same sample is zero.
+ *   y[b][l][co] = bias[co] + sum_{t < K, ci} W[co][ci][t] * frame[b][l*stride + t - pad_l][ci],  l < Lout,
+ *   Lout = (Lc + pad_l + pad_r - K) / stride + 1 (checked),
+ *   v = act(y + addend[b][ol][co]),  ol = l*out_os + out_off; rows with ol outside [0, out_L) are dropped,
+ *   out[b][ol][co] = v, or += v with accumulate.  addend (or NULL) is laid out like out.
+ * K in 1..4, stride in {1, 2}, out_os in {1, 2}; Cin, Cout >= 1 (no multiple required: the packed weight and the
+ * staged tiles are zero-padded).  A k4/s2 transposed conv is its two 2-tap phases with out_os = 2; a conv's input
+ * gradient is this entry over dy with a derived weight (nps_hip/autograd.py Conv1dFn / ConvTranspose1dFn). */
+typedef struct {
+    const float* ptr; int C, L, off;
+} nps_src1_t;
+typedef struct {
+    int nsrc;
+    nps_src1_t src[NPS_MAX_SRC];
+    int B, Lc, Cin;                           /* Cin = sum of the sources' C */
+    int K, stride, pad_l, pad_r, Lout;
+    const float* wpack;                       /* nps_conv1d_pack_weights of W [Cout][Cin][K] */
+    const float* bias;                        /* [Cout] or NULL */
+    int Cout;
+    float* out; int out_C, out_L, out_os, out_off;   /* out [B][out_L][out_C], out_C >= Cout */
+    int accumulate;
+    const float* addend;
+    int act;                                  /* 0 none, 1 GELU (erf) */
+} nps_conv1d_t;
+/* floats of the packing [K][Cin padded to 16][Cout padded to 64] */
+size_t nps_conv1d_packed_floats(int Cout, int Cin, int K);
+int nps_conv1d_pack_weights(const float* w, float* wpack, int Cout, int Cin, int K, void* stream);
+int nps_conv1d_fwd(const nps_conv1d_t* p, void* stream);
+/* Weight gradient: g[m][n][t] = sum_{b,l} a[b][l][m] * xz[b][l*stride + t - pad_l][n] (xz = x, zero outside [0, Lx));
+ * La = (Lx + pad_l + pad_r - K) / stride + 1 (checked).  With a = dy, x = the conv's input: nn.Conv1d.weight.grad
+ * [Cout][Cin][K]; with K = 4, stride = 2, a = a k4/s2 transposed conv's input and x = dy: nn.ConvTranspose1d
+ * .weight.grad [Cin][Cout][4].  The (b, l) reduction is split over work-groups by a schedule fixed by the shape;
+ * every split stores its partial to ws [nps_conv1d_wgrad_ws_floats(p)] and a second launch sums them in split order
+ * and stores g (no atomics: two runs give identical bits). */
+typedef struct {
+    const float* a; int B, La, M;             /* [B][La][M] */
+    const float* x; int Lx, N;                /* [B][Lx][N] */
+    int K, stride, pad_l, pad_r;
+    float* g;                                 /* [M][N][K], stored */
+    float* ws;
+} nps_wgrad1d_t;
+size_t nps_conv1d_wgrad_ws_floats(const nps_wgrad1d_t* p);   /* 0 where nps_conv1d_wgrad would refuse p */
+int nps_conv1d_wgrad(const nps_wgrad1d_t* p, void* stream);
+
 const char* nps_last_error(void);
 const char* nps_version(void);
 

@@ -622,8 +622,11 @@ bool x3_eligible(const nps_conv2d_t& a) {
     const bool geo = a.stride == 1 && a.KH == a.KW &&
                      ((a.dil == 1 && (nt == 1 || nt == 4 || nt == 9)) || (nt == 25 && a.dil >= 1));
     if (a.gn_stats == nullptr && a.pre_act == 0) return geo;
-    // fused prologue: the 3x3 producers, and the 1x1 LDS-weight kernel (its launcher checks Cout <= 192)
-    return geo && (nt == 9 || nt == 1) && (a.pre_act == 0 || a.pre_act == 1) &&
+    // fused prologue: the 3x3 producers, and the 1x1 LDS-weight kernel (its launcher checks Cout <= 192).  The 1x1
+    // kernel's prologue takes its input range from the GroupNorm affine (gn_prologue_scale reads gamma and beta), so
+    // it needs a GroupNorm: an activation-only 1x1 prologue (a norm=False U-Net's final 1x1 conv) is fed by
+    // nps_frame_pack instead
+    return geo && (nt == 9 || (nt == 1 && a.gn_stats != nullptr)) && (a.pre_act == 0 || a.pre_act == 1) &&
            (a.gn_stats == nullptr || (a.gn_groups > 0 && a.Cin % a.gn_groups == 0 && (a.Cin / a.gn_groups) % 4 == 0));
 }
 

@@ -319,31 +319,127 @@ class Conv3d(_Packed3Mixin, _PackedMixin, nn.Conv3d):
 
 class Conv1d(_PackedMixin, nn.Conv1d):
     """nn.Conv1d parameters (common.py:37-47 with spatial_dim 1).  The FNO-1D pointwise `w` conv (fno_kernel_size 1)
-    runs as a 1x1 conv over the (B, 1, L, C) view of channels-last activations on the 2-D HIP conv kernels
-    (run / run_ad); every other geometry keeps nn.Conv1d's own forward."""
+    runs as a 1x1 conv over the (B, 1, L, C) view of channels-last activations on the 2-D HIP conv kernels; the 1-D
+    U-Net's zero-padded k-tap convs (K <= 4, stride 1 or 2) run on the Conv1d kernels that tile along L
+    (nps_conv1d_fwd), in fp32 (run / run_ad).  forward() of every non-pointwise geometry stays nn.Conv1d's own."""
+
+    # set by the 1-D U-Net on its own pointwise convs (shortcuts, the final 1x1): they run on the exact-fp32 Conv1d
+    # kernels with K = 1 like the k-tap convs around them, so that the U-Net's gradients carry fp32 rounding only (the
+    # 2-D route's split-fp16 input gradients cost the parameter gradients behind them up to 1.7e-5); the FNO's `w`
+    # keeps the 2-D route
+    exact = False
 
     def pointwise(self):
         return (tuple(self.kernel_size) == (1,) and tuple(self.stride) == (1,) and tuple(self.dilation) == (1,)
                 and self.groups == 1)
 
+    def _taps(self):
+        """True when run / run_ad take the Conv1d kernels (nps_conv1d_fwd)."""
+        return self.padding_mode == "zeros" and (self.exact or not self.pointwise())
+
     def _check(self):
         if not self.pointwise():
             raise NotImplementedError("only pointwise (kernel 1) 1-D convs run on the MI355X path")
 
+    def geometry1d(self):
+        """(K, stride, pad_left, pad_right) of a zero-padded k-tap conv; every other geometry is refused (the message
+        names the pointwise route, the one a circular conv could take with kernel 1)."""
+        K, s = self.kernel_size[0], self.stride[0]
+        if self.padding_mode != "zeros" or tuple(self.dilation) != (1,) or self.groups != 1 or K > 4 or s > 2:
+            raise NotImplementedError(
+                "1-D convs on the MI355X path: pointwise (kernel 1), or zero-padded with K <= 4, stride 1 or 2, no "
+                f"dilation or groups; got kernel {K}, stride {s}, dilation {self.dilation[0]}, groups {self.groups}, "
+                f"padding_mode {self.padding_mode!r}")
+        if self.padding == "same":
+            return K, s, (K - 1) // 2, K - 1 - (K - 1) // 2
+        if self.padding == "valid":
+            return K, s, 0, 0
+        if s == 1 and self.padding[0] > K - 1:  # (the stride-1 input gradient pads dy by K - 1 - padding)
+            raise NotImplementedError(f"1-D convs on the MI355X path: stride-1 padding {self.padding[0]} exceeds "
+                                      f"kernel {K} - 1 (pointwise convs take no padding)")
+        return K, s, self.padding[0], self.padding[0]
+
     def geometry(self):
-        return 1, 1, 1, 1, (0, 0), (0, 0), 0
+        if self.pointwise():
+            return 1, 1, 1, 1, (0, 0), (0, 0), 0
+        K, s, pl, pr = self.geometry1d()
+        return 1, K, s, 1, (0, pl), (0, pr), 0
+
+    def out_hw(self, H, W):
+        """Output size of this conv on a (1, L) frame."""
+        if self.pointwise():
+            return H, W
+        K, s, pl, pr = self.geometry1d()
+        return H, (W + pl + pr - K) // s + 1
+
+    def _run_taps(self, srcs, frame_hw, gn=None, pre_act=0, out=None, out_off=(0, 0), accumulate=False, addends=(),
+                  act=0, out_stats=None):
+        """The k-tap route of run(): ops.conv2d's keywords on nps_conv1d_fwd.  A GroupNorm / activation prologue is
+        materialised first (ops.frame_pack); the launch produces no GroupNorm moments (out_stats is marked
+        incomplete: the next norm takes its statistics pass)."""
+        K, s, pl, pr = self.geometry1d()
+        if frame_hw[0] != 1 or len(addends) > 1:
+            raise NotImplementedError("1-D convs take (1, L) frames and at most one addend")
+        if gn is not None or pre_act:
+            srcs = [ops.Src(ops.frame_pack(srcs, frame_hw, gn, pre_act))]
+        if out_stats is not None:
+            out_stats._nps_incomplete = True
+        out3 = ad3 = None
+        if out is not None:
+            if out_off[0] != 0 or out.dim() != 4 or out.shape[1] != 1:
+                raise RuntimeError("1-D conv: out must be a (B, 1, L, C) map written at row 0")
+            ops.drop_stats(out)
+            ops.drop_tag(out)
+            out3 = out.view(out.shape[0], out.shape[2], out.shape[3])
+        if len(addends) == 1:
+            ad3 = addends[0].view(addends[0].shape[0], addends[0].shape[2], addends[0].shape[3])
+        y = ops.conv1d(srcs, frame_hw[1], self._packed(ops.pack_conv1d_weight, "conv1"), self.bias, self.out_channels,
+                       K, stride=s, pad=(pl, pr), out=out3, out_off=out_off[1], accumulate=accumulate, addend=ad3,
+                       act=act)
+        return out if out is not None else y.view(y.shape[0], 1, y.shape[1], y.shape[2])
 
     def run(self, srcs, frame_hw, **kw):
         """srcs: (B, L, C) sources viewed as (B, 1, L, C); frame_hw = (1, L)."""
+        if self._taps():
+            return self._run_taps(srcs, frame_hw, **kw)
         self._check()
         pk = self._packed(lambda w: ops.pack_conv_weight(w.reshape(w.shape[0], w.shape[1], 1, 1)), "conv1d")
         return ops.conv2d(srcs, frame_hw, pk, self.bias, self.out_channels, 1, 1, **kw)
 
     def run_ad(self, x):
         """Differentiable form: x (B, 1, L, Cin)."""
+        if self._taps():
+            return ad.conv1d(self, x)
         self._check()
-        return ad.Conv2dFn.apply(self.geometry(), x, self.weight.reshape(self.out_channels, self.in_channels, 1, 1),
-                                 self.bias)
+        return ad.Conv2dFn.apply((1, 1, 1, 1, (0, 0), (0, 0), 0), x,
+                                 self.weight.reshape(self.out_channels, self.in_channels, 1, 1), self.bias)
+
+
+class ConvTranspose1d(_PackedMixin, nn.ConvTranspose1d):
+    """nn.ConvTranspose1d(k=4, s=2, padding 0 or 1) parameters: the 1-D U-Net Upsample ('ones' mode) as the two 2-tap
+    phase convs of nps_conv1d_fwd, on (B, 1, L, C) fp32 maps."""
+
+    def run(self, x, act=0):
+        ad.check_conv_transpose1d(self)
+        if x.dim() != 4 or x.shape[1] != 1:
+            raise RuntimeError(f"ConvTranspose1d.run: a (B, 1, L, C) map expected, got {tuple(x.shape)}")
+        B, _, L, C = x.shape
+        p = self.padding[0]
+        phases = self._packed(lambda w: [ops.pack_conv1d_weight(q) for q in ops.conv_transpose1d_phase_weights(w)],
+                              "convT1")
+        out = torch.empty((B, 1, 2 * L + 2 - 2 * p, self.out_channels), dtype=torch.float32, device=x.device)
+        for r in (0, 1):
+            ops.conv1d([ops.Src(x)], L, phases[r], self.bias, self.out_channels, 2, pad=(1, 1), out=out[:, 0],
+                       out_os=2, out_off=r - p, act=act)
+        return out
+
+    def run_ad(self, x):
+        return ad.conv_transpose1d(self, x)
+
+    def forward(self, x):
+        """(B, C, L) -> (B, Cout, 2 L + 2 - 2 padding)."""
+        form = AUTOGRAD1D if use_autograd(self) else INFER1D
+        return form.to_out(form.upsample(self, form.to_in(x)))
 
 
 def flat_frame(spatial):
@@ -408,7 +504,7 @@ class ConvTranspose3d_padded(_Packed3Mixin, nn.ConvTranspose3d):
 def get_upconv_with_right_spatial_dim(spatial_dim, in_channels, out_channels, **kwargs):
     """common.py:103-120, plus a 3-D circular form the reference lacks (ConvTranspose3d_padded)."""
     if spatial_dim == 1:
-        return nn.ConvTranspose1d(in_channels, out_channels, **kwargs)
+        return ConvTranspose1d(in_channels, out_channels, **kwargs)
     if spatial_dim == 2:
         if kwargs.get("padding_mode") == "circular":
             kernel_size = kwargs["kernel_size"]
@@ -433,6 +529,7 @@ class Form(NamedTuple):
     upsample: Callable   # (Upsample.conv, h) -> the transposed conv's output
     to_in: Callable      # channels-first -> channels-last at a module boundary
     to_out: Callable     # and back
+    dims: int = 0        # the num_spatial_dims of the models the form serves, when it is not nd (the 1-D forms)
 
 
 def _upsample3d(conv, h):
@@ -447,12 +544,26 @@ INFER3D = Form("run3d", ops.Src3, 3, _upsample3d, to_ndhwc, to_ncdhw)
 # fp32 training in 3-D.  run_form never picks it (the 3-D module boundaries refuse grad mode): UFNO.forward and the
 # NDHWC methods run_ad3d are its entries.
 AUTOGRAD3D = Form("run_ad3d", ops.Src3, 3, ad.conv_transpose3d, ad_to_ndhwc, ad_to_ncdhw)
+# 1-D: (B, C, L) tensors walk as (B, 1, L, C) maps through the 2-D methods (frames, GroupNorm, attention); the convs
+# and the Upsample are the modules' own run / run_ad (Conv1d, ConvTranspose1d).
+INFER1D = Form("run", ops.Src, 2, lambda conv, h: conv.run(h), lambda x: ops.nchw_to_nhwc(x.unsqueeze(2)),
+               lambda y: ops.nhwc_to_nchw(y).squeeze(2), 1)
+AUTOGRAD1D = Form("run_ad", ops.Src, 2, lambda conv, h: conv.run_ad(h), lambda x: ad.to_nhwc(x.unsqueeze(2)),
+                  lambda y: ad.to_nchw(y).squeeze(2), 1)
+
+
+def form_dims(form):
+    """The num_spatial_dims of the models a form serves."""
+    return form.dims or form.nd
 
 
 def run_form(mod, x, vb, fn):
     """The module boundary of a forward(): fn(form, x, vb) on the channels-last x and conditioning vb (or None) in
     the form that x and the grad mode call for; the tensor or tuple of tensors it returns, channels-first."""
-    form = INFER3D if x.dim() == 5 else AUTOGRAD2D if use_autograd(mod) else INFER2D
+    if x.dim() == 3:
+        form = AUTOGRAD1D if use_autograd(mod) else INFER1D
+    else:
+        form = INFER3D if x.dim() == 5 else AUTOGRAD2D if use_autograd(mod) else INFER2D
     if form is INFER3D and use_autograd(mod):
         raise NotImplementedError("the 3-D U-Net is inference-only on the MI355X path (C5 rollout)")
     vb = form.to_in(vb) if vb is not None else None

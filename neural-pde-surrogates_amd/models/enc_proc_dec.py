@@ -142,19 +142,27 @@ class EncProcDec(ModelInterface):
         return self.decoder.run(h, u, final_tanh=final_tanh, mask=mask, mask_ch=mask_channel or 0)
 
     def _check_processors(self):
-        """Off the 2-D grid: FNO in 1-D; FNO, U-FNO and U-Net in 3-D.  Anything else has no HIP path there and is
-        refused before any launch."""
+        """Off the 2-D grid: FNO and the zero-padded (padding_mode "ones") U-Net / U-FNO in 1-D; FNO, U-FNO and U-Net in
+        3-D.  Anything else has no HIP path there and is refused before any launch."""
         nd = self.num_spatial_dims
         if nd == 2:
             return
         if nd not in (1, 3):
             raise NotImplementedError(f"EncProcDec: grids have 1 to 3 spatial axes, got num_spatial_dims={nd}")
         for p in self.processor:
-            if not (isinstance(p, FNO) or (nd == 3 and isinstance(p, (UFNO, UNetModern)))):
+            if not isinstance(p, (FNO, UFNO, UNetModern)):
                 raise NotImplementedError(f"EncProcDec: the processor {type(p).__name__} has no {nd}-D HIP path "
-                                          f"(1-D: FNO; 3-D: FNO, UFNO, UNetModern)")
+                                          f"(1-D: FNO, and UFNO / UNetModern with padding_mode='ones'; 3-D: FNO, UFNO, "
+                                          f"UNetModern)")
             if nd == 1:
-                for layer in p.fno_layers:
+                for unet in [p] if isinstance(p, UNetModern) else getattr(p, "unet_layers", []):
+                    if unet.padding_mode != "ones":
+                        raise NotImplementedError(
+                            f"EncProcDec: the processor {type(p).__name__} has no 1-D HIP path with padding_mode="
+                            f"{unet.padding_mode!r}: the 1-D HIP path is the zero-padded padding_mode='ones' U-Net "
+                            "(the reference cannot build a circular 1-D U-Net of more than one level: "
+                            "nn.ConvTranspose1d takes zero padding only)")
+                for layer in getattr(p, "fno_layers", []):
                     layer._check_1d()  # fno_kernel_size > 1
 
     def _process(self, p, h, vb, spatial, train):
@@ -165,6 +173,8 @@ class EncProcDec(ModelInterface):
         if isinstance(p, FNO):
             kw = dict(D=spatial[0]) if nd == 3 else {}
             return p.run_ad(h, vb, **kw) if train else p.run(h, vb, **kw)
+        if nd == 1:  # the 1-D U-Net / U-FNO walk the (B, 1, L, C) maps themselves
+            return p.run_ad(h, vb) if train else p.run(h, vb)
         # the 3-D U-Net / U-FNO walk NDHWC volumes
         ndhwc = lambda t: ops.pixel_view(t, (t.shape[0],) + tuple(spatial) + (t.shape[3],))  # noqa: E731
         h5, vb5 = ndhwc(h), ndhwc(vb) if vb is not None else None

@@ -134,6 +134,16 @@ class UFNO(nn.Module):
             if vb is not None and vb.dtype != h.dtype:  # conditioning in the activations' storage dtype
                 vb = ops.to_bf16(vb) if h.dtype == torch.bfloat16 else ops.to_f32(vb)
             return to_ncdhw(self.run3d(to_ndhwc(h), vb))
+        if self.num_spatial_dims == 1:  # (B, C, L): the blocks run on the (B, 1, L, C) view
+            for unet in self.unet_layers:
+                unet.check_1d()  # a circular 1-D U-Net raises before any work
+            for layer in self.fno_layers:
+                layer._check_1d()  # fno_kernel_size > 1
+            vb = variables_broadcast.unsqueeze(2) if variables_broadcast is not None else None
+            return self._forward2d(h.unsqueeze(2), vb).squeeze(2)
+        return self._forward2d(h, variables_broadcast)
+
+    def _forward2d(self, h, variables_broadcast):
         if use_autograd(self):
             vb = ad.to_nhwc(variables_broadcast) if variables_broadcast is not None else None
             return ad.to_nchw(self.run_ad(ad.to_nhwc(h), vb))

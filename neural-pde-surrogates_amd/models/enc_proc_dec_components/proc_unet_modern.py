@@ -12,7 +12,10 @@ chain of fused HIP launches on NHWC tensors:
 
 The model runs in four forms (models.common.Form): 2-D inference (`run`, the fused launches above), 2-D
 autograd (`run_ad`, the same kernels unfused plus their backward kernels), 3-D inference (`run3d`, NDHWC) and 3-D
-autograd (`run_ad3d`, NDHWC fp32).
+autograd (`run_ad3d`, NDHWC fp32).  A 1-D U-Net (padding_mode "ones": every conv zero-padded) walks (B, 1, L, C)
+maps through the 2-D methods in the two 1-D forms: frames, GroupNorm and attention are the 2-D launches; its convs —
+k-tap, the pointwise shortcuts and final conv (Conv1d.exact) — and its Upsample are Conv1d / ConvTranspose1d's own
+run / run_ad (the Conv1d kernels that tile along L, exact fp32, no fused prologue and no carried moments).
 The down / middle / up traversal is written once, `UNetModern._walk(form, h, vb)`, and so is each
 Down / MiddleBlock body (`_run(form, x, vb)`); a form names the per-module method, the source tuple, the number
 of spatial dims and how an Upsample is applied.  What differs by algorithm stays written per form: the three
@@ -27,7 +30,8 @@ from torch import nn
 
 from common.interfaces import D, M
 from models.common import (get_conv_with_right_spatial_dim, get_upconv_with_right_spatial_dim, crop_offsets,
-                           activation_code, run_form, INFER2D, AUTOGRAD2D, INFER3D, AUTOGRAD3D)
+                           activation_code, run_form, form_dims, INFER1D, AUTOGRAD1D, INFER2D, AUTOGRAD2D, INFER3D,
+                           AUTOGRAD3D)
 from nps_hip import ops
 from nps_hip import autograd as ad
 from pdes import PDE
@@ -110,13 +114,17 @@ class UNetModern(nn.Module):
         else:
             self.final = get_conv_with_right_spatial_dim(num_spatial_dims, in_channels=hidden_features,
                                                          out_channels=hidden_features, kernel_size=3, **padding_kwargs)
+        if num_spatial_dims == 1:
+            self.final.exact = True  # (a pointwise final conv on the exact-fp32 Conv1d kernels: models.common.Conv1d)
 
     def _walk(self, form, h, vb):
         """Down, middle and up (proc_unet_modern.py:169-193) in the given form.  Returns the last feature map and the
         input's shape (the final conv's crop target)."""
-        if self.num_spatial_dims != form.nd:
+        if self.num_spatial_dims != form_dims(form):
             raise NotImplementedError("UNetModern: 2-D only on the MI355X path" if form.nd == 2 else
                                       "UNetModern.run3d: 3-D U-Nets only")
+        if self.num_spatial_dims == 1:
+            self.check_1d()
         if self.n_cond > 0 and vb is None:
             # reference Downsample.forward returns a bare tensor here (proc_unet_modern.py:451-455) which
             # :175 then unpacks along the batch dimension; refuse instead of reproducing that bug
@@ -145,11 +153,19 @@ class UNetModern(nn.Module):
                 h = _res_attn(form, m, m.res, srcs, size)
         return h, h_shape
 
+    def check_1d(self):
+        """The 1-D U-Net on the HIP path is the zero-padded one."""
+        if self.padding_mode != "ones":
+            raise NotImplementedError(
+                f"UNetModern: the 1-D HIP path is the zero-padded padding_mode='ones' U-Net, got "
+                f"{self.padding_mode!r} (the reference cannot build a circular 1-D U-Net of more than one level: "
+                "nn.ConvTranspose1d takes zero padding only)")
+
     def run(self, h, vb, addend=None, act_after=0, addend_fork=None):
         """NHWC forward (proc_unet_modern.py:169-196).  Optional fused epilogue on the final conv:
         out = act_after(final(...) + addend) — the U-FNO block combination.  addend_fork: the ops.Fork whose
         side stream computes addend (joined just before the final conv)."""
-        h, h_shape = self._walk(INFER2D, h, vb)
+        h, h_shape = self._walk(INFER1D if self.num_spatial_dims == 1 else INFER2D, h, vb)
         # final: conv(act(norm(h))) then crop_Nd to the input size, as one launch
         H, W = h.shape[1:3]
         gn = None
@@ -171,9 +187,9 @@ class UNetModern(nn.Module):
 
     def run_ad(self, h, vb):
         """Differentiable NHWC forward (training): proc_unet_modern.py:169-196 as unfused HIP ops."""
-        h, h_shape = self._walk(AUTOGRAD2D, h, vb)
+        h, h_shape = self._walk(AUTOGRAD1D if self.num_spatial_dims == 1 else AUTOGRAD2D, h, vb)
         norm = self.norm if isinstance(self.norm, nn.GroupNorm) else None
-        y = ad.conv2d(self.final, ad.frame([ops.Src(h)], h.shape[1:3], norm, activation_code(self.activation)))
+        y = self.final.run_ad(ad.frame([ops.Src(h)], h.shape[1:3], norm, activation_code(self.activation)))
         return ad.crop(y, h_shape[1:3], crop_offsets(y.shape[1:3], h_shape[1:3]))
 
     def run3d(self, h, vb, addend=None, act_after=0, addend_fork=None):
@@ -209,6 +225,8 @@ class UNetModern(nn.Module):
 
     def forward(self, h: torch.Tensor, variables_broadcast: torch.Tensor = None, pos=None):
         assert h.dim() == 2 + self.num_spatial_dims
+        if self.num_spatial_dims == 1:
+            self.check_1d()  # a circular 1-D U-Net raises before any work
         return run_form(self, h, variables_broadcast, lambda form, h, vb: getattr(self, form.run)(h, vb))
 
 
@@ -227,6 +245,8 @@ class ResidualBlock(nn.Module):
         if in_channels != out_channels:
             self.shortcut = get_conv_with_right_spatial_dim(num_spatial_dims, in_channels=in_channels,
                                                             out_channels=out_channels, kernel_size=1)
+            if num_spatial_dims == 1:
+                self.shortcut.exact = True  # (on the exact-fp32 Conv1d kernels: models.common.Conv1d)
         else:
             self.shortcut = nn.Identity()
         if norm:
@@ -340,12 +360,12 @@ class ResidualBlock(nn.Module):
         # conv1's frame and the shortcut's input (x itself for the identity) from one node: the backward adds the
         # shortcut path's gradient inside the frame backward (ad.frame_pair), not as a separate accumulation
         f1, xin = ad.frame_pair(srcs, (H, W), n1, act) if ad.FRAME_PAIR else (ad.frame(srcs, (H, W), n1, act), None)
-        h1 = ad.conv2d(self.conv1, f1)
+        h1 = self.conv1.run_ad(f1)
         if isinstance(self.shortcut, nn.Identity):
             sc = xin if xin is not None else srcs[0].t
         else:
-            sc = ad.conv2d(self.shortcut, xin if xin is not None else ad.frame(srcs, (H, W)))
-        h2 = ad.conv2d(self.conv2, ad.frame([ops.Src(h1)], h1.shape[1:3], n2, act))
+            sc = self.shortcut.run_ad(xin if xin is not None else ad.frame(srcs, (H, W)))
+        h2 = self.conv2.run_ad(ad.frame([ops.Src(h1)], h1.shape[1:3], n2, act))
         return ad.add_at(sc, h2, crop_offsets(h2.shape[1:3], sc.shape[1:3]))
 
     def run_ad3d(self, srcs, frame_dhw):
@@ -444,8 +464,8 @@ class AttentionBlock(nn.Module):
         return ad.add_at(sc, y)
 
     def forward(self, x: torch.Tensor):
-        if x.dim() != 4:
-            raise NotImplementedError("U-Net attention: 2-D maps only on the MI355X path")
+        if x.dim() not in (3, 4):
+            raise NotImplementedError("U-Net attention: 1-D and 2-D maps only on the MI355X path")
         return run_form(self, x, None, lambda form, x, _: getattr(self, form.run)(x))
 
 
@@ -538,9 +558,9 @@ class Downsample(nn.Module):
         return h, vb
 
     def run_ad(self, x, vb):
-        h = ad.conv2d(self.conv, x)
+        h = self.conv.run_ad(x)
         if vb is not None:
-            vb = ad.conv2d(self.conv_variables_broadcast, vb)
+            vb = self.conv_variables_broadcast.run_ad(vb)
         return h, vb
 
     def run3d(self, x, vb):

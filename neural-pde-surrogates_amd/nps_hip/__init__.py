@@ -13,7 +13,7 @@ import os
 
 import torch
 
-__all__ = ["lib", "Src", "Conv2dArgs", "WgradArgs", "Wgrad3dArgs", "Src3", "Conv3dArgs", "PackJob", "check", "stream_ptr", "ptr", "LIB_PATH"]
+__all__ = ["lib", "Src", "Conv2dArgs", "WgradArgs", "Wgrad3dArgs", "Src3", "Conv3dArgs", "Src1", "Conv1dArgs", "Wgrad1dArgs", "PackJob", "check", "stream_ptr", "ptr", "LIB_PATH"]
 
 LIB_PATH = os.environ.get("NPS_HIP_LIB", os.path.join(os.path.dirname(os.path.abspath(__file__)), "libnps_hip.so"))
 if not os.path.exists(LIB_PATH):
@@ -96,6 +96,31 @@ class Wgrad3dArgs(ctypes.Structure):
         ("x", ctypes.c_void_p), ("Dx", ctypes.c_int), ("Hx", ctypes.c_int), ("Wx", ctypes.c_int), ("N", ctypes.c_int),
         ("K", ctypes.c_int), ("stride", ctypes.c_int), ("circ", ctypes.c_int), ("zpad", ctypes.c_int),
         ("g", ctypes.c_void_p),
+    ]
+
+
+class Src1(ctypes.Structure):
+    _fields_ = [("ptr", ctypes.c_void_p), ("C", ctypes.c_int), ("L", ctypes.c_int), ("off", ctypes.c_int)]
+
+
+class Conv1dArgs(ctypes.Structure):
+    _fields_ = [
+        ("nsrc", ctypes.c_int), ("src", Src1 * MAX_SRC),
+        ("B", ctypes.c_int), ("Lc", ctypes.c_int), ("Cin", ctypes.c_int),
+        ("K", ctypes.c_int), ("stride", ctypes.c_int), ("pad_l", ctypes.c_int), ("pad_r", ctypes.c_int),
+        ("Lout", ctypes.c_int),
+        ("wpack", ctypes.c_void_p), ("bias", ctypes.c_void_p), ("Cout", ctypes.c_int),
+        ("out", ctypes.c_void_p), ("out_C", ctypes.c_int), ("out_L", ctypes.c_int), ("out_os", ctypes.c_int),
+        ("out_off", ctypes.c_int), ("accumulate", ctypes.c_int), ("addend", ctypes.c_void_p), ("act", ctypes.c_int),
+    ]
+
+
+class Wgrad1dArgs(ctypes.Structure):
+    _fields_ = [
+        ("a", ctypes.c_void_p), ("B", ctypes.c_int), ("La", ctypes.c_int), ("M", ctypes.c_int),
+        ("x", ctypes.c_void_p), ("Lx", ctypes.c_int), ("N", ctypes.c_int),
+        ("K", ctypes.c_int), ("stride", ctypes.c_int), ("pad_l", ctypes.c_int), ("pad_r", ctypes.c_int),
+        ("g", ctypes.c_void_p), ("ws", ctypes.c_void_p),
     ]
 
 
@@ -238,6 +263,12 @@ _SIGS = {
                              _vp]),
     "nps_add_at_copy3d": (_i, [_vp, _vp, _vp] + [_i] * 11 + [_vp]),
     "nps_frame3d_locate": (_i, [ctypes.POINTER(Conv3dArgs), _i, _i, _i, _i] + [ctypes.POINTER(_i)] * 3),
+    # 1-D U-Net convs (k-tap Conv1d along L)
+    "nps_conv1d_packed_floats": (_sz, [_i, _i, _i]),
+    "nps_conv1d_pack_weights": (_i, [_vp, _vp, _i, _i, _i, _vp]),
+    "nps_conv1d_fwd": (_i, [ctypes.POINTER(Conv1dArgs), _vp]),
+    "nps_conv1d_wgrad_ws_floats": (_sz, [ctypes.POINTER(Wgrad1dArgs)]),
+    "nps_conv1d_wgrad": (_i, [ctypes.POINTER(Wgrad1dArgs), _vp]),
     # U-Net self-attention (column softmax), flash-style
     "nps_attn_colstats": (_i, [_vp, _vp, _i, _i, _i, _i, ctypes.c_float, _vp]),
     "nps_attn_fwd": (_i, [_vp, _vp, _vp, _i, _i, _i, _i, ctypes.c_float, _vp]),

@@ -617,6 +617,146 @@ def conv_transpose3d(conv, x: torch.Tensor) -> torch.Tensor:
     return ConvTranspose3dFn.apply((conv.pad,), x, conv.weight, conv.bias)
 
 
+# ------------------------------------------------------------------------- 1-D conv (k taps along L)
+def _check_geo1(geo):
+    """The 1-D conv geometries that run: K in 1..4 at stride 1 zero-padded by at most K - 1 per side, or stride 2."""
+    K, s, pl, pr = geo
+    ok = 1 <= K <= 4 and s in (1, 2) and pl >= 0 and pr >= 0 and (s == 2 or (pl <= K - 1 and pr <= K - 1))
+    if not ok:
+        raise NotImplementedError(f"1-D conv: K={K} stride={s} padding=({pl}, {pr}) is not supported")
+
+
+def _fp32_1d(x, weight, what):
+    if not (x.is_cuda and weight.is_cuda):
+        raise RuntimeError(f"nps_hip ops run on the MI355X only: {what} got a tensor on {x.device} / {weight.device}")
+    if x.dtype != torch.float32 or weight.dtype != torch.float32:
+        raise NotImplementedError(f"{what}: the 1-D convs run fp32 tensors only")
+    if x.dim() != 4 or x.shape[1] != 1:
+        raise RuntimeError(f"{what}: a (B, 1, L, C) input expected, got {tuple(x.shape)}")
+
+
+def _rows(x):
+    """(B, 1, L, C) -> the contiguous (B, L, C) view."""
+    x = _c(x)
+    return x.view(x.shape[0], x.shape[2], x.shape[3])
+
+
+def _map(y):
+    """(B, L, C) -> (B, 1, L, C)."""
+    return y.view(y.shape[0], 1, y.shape[1], y.shape[2])
+
+
+def _pack1_phases(w):
+    return [ops.pack_conv1d_weight(p) for p in ops.conv_transpose1d_phase_weights(w)]
+
+
+def _conv_transpose1d_fwd(x3, phases, bias, Cout, p):
+    """The k4/s2 transposed conv (padding p) of x3 (B, L, Cin) as its two 2-tap phases, written interleaved."""
+    B, L, _ = x3.shape
+    out = torch.empty((B, 2 * L + 2 - 2 * p, Cout), dtype=torch.float32, device=x3.device)
+    for r in (0, 1):  # q in [0, L]: positions -p .. 2 L + 1 - p, every element of out once
+        ops.conv1d([ops.Src1(x3)], L, phases[r], bias, Cout, 2, pad=(1, 1), out=out, out_os=2, out_off=r - p)
+    return out
+
+
+class Conv1dFn(torch.autograd.Function):
+    """nn.Conv1d forward/backward on (B, 1, L, C) fp32 maps (models/common.py Conv1d.run_ad): geo = (K, stride,
+    pad_left, pad_right), zero padding.  Input gradient = nps_conv1d_fwd launches on dy — stride 1: the conv with
+    flipped, channel-swapped taps padded by K - 1 - pad; stride 2: the two 2-tap phases (out_os = 2) of the
+    transposed conv whose weight is the conv's own, shifted by -pad_left and cropped to x.  Weight gradient =
+    nps_conv1d_wgrad, bias gradient = channel_sums."""
+
+    @staticmethod
+    def forward(ctx, geo, x, weight, bias):
+        _check_geo1(geo)
+        _fp32_1d(x, weight, "Conv1dFn")
+        K, s, pl, pr = geo
+        x3 = _rows(x)
+        y = ops.conv1d([ops.Src1(x3)], x3.shape[1], ops.cached_pack(weight, "conv1", ops.pack_conv1d_weight), bias,
+                       weight.shape[0], K, stride=s, pad=(pl, pr))
+        ctx.geo, ctx.has_bias = geo, bias is not None
+        ctx.param = weight  # the nn.Parameter itself: its input-gradient packings are cached on it
+        ctx.save_for_backward(x3, weight)
+        return _map(y)
+
+    @staticmethod
+    def backward(ctx, gy):
+        K, s, pl, pr = ctx.geo
+        x3, w = ctx.saved_tensors
+        gy = _rows(gy)
+        B, L, Cin = x3.shape
+        Ly = gy.shape[1]
+        dx = dw = db = None
+        if ctx.needs_input_grad[1]:
+            if s == 1:
+                wd = ops.cached_pack(ctx.param, "dgrad1",
+                                     lambda p: ops.pack_conv1d_weight(ops.conv1d_dgrad_weight(p)))
+                dx = ops.conv1d([ops.Src1(gy)], Ly, wd, None, Cin, K, pad=(K - 1 - pl, K - 1 - pr))
+            else:
+                # dx[i] = sum over 2 o + t - pl = i of dy[o] w[:, :, t]: the stride-2 transposed conv of dy with the
+                # conv's own weight as (in = Cout, out = Cin, k); positions 2 q + r - pl, q in [0, Ly]
+                ph = ops.cached_pack(ctx.param, "dgrad1_s2", _pack1_phases)
+                covered = 2 * Ly + 1 - pl >= L - 1
+                dx = (torch.empty if covered else torch.zeros)((B, L, Cin), dtype=torch.float32, device=gy.device)
+                for r in (0, 1):
+                    ops.conv1d([ops.Src1(gy)], Ly, ph[r], None, Cin, 2, pad=(1, 1), out=dx, out_os=2, out_off=r - pl)
+            dx = _map(dx)
+        if ctx.needs_input_grad[2]:
+            dw = ops.conv1d_wgrad(gy, x3, K, stride=s, pad=(pl, pr))
+        if ctx.has_bias and ctx.needs_input_grad[3]:
+            db = channel_sums(gy)
+        return None, dx, dw, db
+
+
+class ConvTranspose1dFn(torch.autograd.Function):
+    """nn.ConvTranspose1d(k=4, s=2, padding p in {0, 1}) on (B, 1, L, C) fp32 maps: the two 2-tap phases of
+    nps_conv1d_fwd.  The input gradient is the K = 4 / stride-2 / pad-p conv of dy with the parameter read as
+    (out = Cin, in = Cout, k); the weight gradient is nps_conv1d_wgrad with the roles swapped (a = x, x = dy)."""
+
+    @staticmethod
+    def forward(ctx, p, x, weight, bias):
+        _fp32_1d(x, weight, "ConvTranspose1dFn")
+        x3 = _rows(x)
+        out = _conv_transpose1d_fwd(x3, ops.cached_pack(weight, "convT1", _pack1_phases), bias, weight.shape[1], p)
+        ctx.p, ctx.has_bias = p, bias is not None
+        ctx.param = weight
+        ctx.save_for_backward(x3, weight)
+        return _map(out)
+
+    @staticmethod
+    def backward(ctx, gout):
+        p = ctx.p
+        x3, w = ctx.saved_tensors
+        gout = _rows(gout)
+        Cin = x3.shape[2]
+        dx = dw = db = None
+        if ctx.needs_input_grad[1]:
+            wd = ops.cached_pack(ctx.param, "dgradT1", ops.pack_conv1d_weight)
+            dx = _map(ops.conv1d([ops.Src1(gout)], gout.shape[1], wd, None, Cin, 4, stride=2, pad=(p, p)))
+        if ctx.needs_input_grad[2]:
+            dw = ops.conv1d_wgrad(x3, gout, 4, stride=2, pad=(p, p))
+        if ctx.has_bias and ctx.needs_input_grad[3]:
+            db = channel_sums(gout)
+        return None, dx, dw, db
+
+
+def check_conv_transpose1d(conv):
+    if (tuple(conv.kernel_size) != (4,) or tuple(conv.stride) != (2,) or conv.padding[0] not in (0, 1)
+            or tuple(conv.output_padding) != (0,) or tuple(conv.dilation) != (1,) or conv.groups != 1):
+        raise NotImplementedError("1-D Upsample: ConvTranspose1d(k=4, s=2, padding 0 or 1) only on the MI355X path")
+
+
+def conv1d(conv, x: torch.Tensor) -> torch.Tensor:
+    """Differentiable forward of a zero-padded k-tap models.common.Conv1d on a (B, 1, L, C) fp32 map."""
+    return Conv1dFn.apply(conv.geometry1d(), x, conv.weight, conv.bias)
+
+
+def conv_transpose1d(conv, x: torch.Tensor) -> torch.Tensor:
+    """Differentiable forward of a models.common.ConvTranspose1d on a (B, 1, L, C) fp32 map."""
+    check_conv_transpose1d(conv)
+    return ConvTranspose1dFn.apply(conv.padding[0], x, conv.weight, conv.bias)
+
+
 # ------------------------------------------------------------------------- 3-D frame (cat/crop/GN/GELU)
 def _frame3d_fwd(meta, gamma, beta, srcs):
     """The forward shared by Frame3dFn / FramePair3dFn: (Src3 sources, GN or None, act(GN(frame)))."""

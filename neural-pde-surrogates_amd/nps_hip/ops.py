@@ -13,7 +13,7 @@ from typing import List, NamedTuple, Optional, Sequence, Union
 
 import torch
 
-from . import Conv2dArgs, Conv3dArgs, PackJob, Wgrad3dArgs, Src as _CSrc, Src3 as _CSrc3, check, lib, ptr, stream_ptr
+from . import Conv1dArgs, Conv2dArgs, Conv3dArgs, PackJob, Wgrad1dArgs, Wgrad3dArgs, Src as _CSrc, Src3 as _CSrc3, check, lib, ptr, stream_ptr
 
 GELU = 1
 
@@ -1525,6 +1525,157 @@ def circular_fold3d(gp: torch.Tensor, pad: int) -> torch.Tensor:
     out = torch.empty((B, D, H, W, C), dtype=torch.float32, device=gp.device)
     check(lib.nps_circular_fold3d(ptr(gp), ptr(out), B, D, H, W, C, pad, stream_ptr()), "circular_fold3d")
     return out
+
+
+# ------------------------------------------------------------ 1-D U-Net convs -----
+class Src1(NamedTuple):
+    t: torch.Tensor          # (B, L, C) channels-last contiguous fp32
+    off: int = 0             # placement along L inside the frame (crop_Nd: > 0 zero-pads, < 0 crops)
+
+
+def drop_tag(t: torch.Tensor):
+    """Forget t's range tag: a kernel that knows no tags wrote into t."""
+    if getattr(t, "_nps_tag", None) is not None:
+        t._nps_tag = None
+
+
+def _check1d(t: torch.Tensor, what: str):
+    if not t.is_cuda:
+        raise RuntimeError(f"nps_hip ops run on the MI355X only: {what} is on {t.device}")
+    if t.dtype != torch.float32:
+        raise NotImplementedError(f"nps_hip {what}: the 1-D convs run fp32 tensors only, got {t.dtype}")
+
+
+def _src1(s) -> Src1:
+    """An ops.Src1, or an ops.Src of a (B, 1, L, C) map (its off_x is the offset along L), as a Src1 of (B, L, C)."""
+    t = s.t
+    off = s.off if isinstance(s, Src1) else s.off_x
+    if t.dim() == 4:
+        if t.shape[1] != 1 or (not isinstance(s, Src1) and s.off_y):
+            raise RuntimeError(f"nps_hip conv1d: a 4-D source must be a (B, 1, L, C) map at row 0, got {tuple(t.shape)}")
+        t = t.view(t.shape[0], t.shape[2], t.shape[3])
+    return Src1(t, int(off))
+
+
+def pack_conv1d_weight(w: torch.Tensor) -> torch.Tensor:
+    """A conv weight (Cout, Cin, K) -> the nps_conv1d packing [K][Cin padded to 16][Cout padded to 64] (zeros in the
+    padding)."""
+    _check1d(w, "pack_conv1d_weight weight")
+    w = w.detach().contiguous()
+    Cout, Cin, K = w.shape
+    n = lib.nps_conv1d_packed_floats(Cout, Cin, K)
+    if n == 0:
+        raise RuntimeError(f"nps_hip pack_conv1d_weight: unsupported weight shape {tuple(w.shape)} (K in 1..4)")
+    out = torch.empty(n, dtype=torch.float32, device=w.device)
+    check(lib.nps_conv1d_pack_weights(ptr(w), ptr(out), Cout, Cin, K, stream_ptr()), "conv1d_pack_weights")
+    out.nps_conv1d = (Cout, Cin, K)
+    return out
+
+
+def conv1d(srcs, L: int, wpack: torch.Tensor, bias: Optional[torch.Tensor], Cout: int, K: int, stride=1, pad=(0, 0),
+           out: Optional[torch.Tensor] = None, out_os=1, out_off=0, accumulate=False,
+           addend: Optional[torch.Tensor] = None, act=0) -> torch.Tensor:
+    """One nps_conv1d_fwd launch over a virtual channels-last frame of L positions (sources Src1 / (B, 1, L, C) Src at
+    their crop offsets, zero outside themselves and outside the frame): the K-tap conv with stride 1 or 2 and
+    (left, right) zero padding `pad`; out[b][l*out_os + out_off] = act(conv + bias + addend) (+= with accumulate),
+    rows outside out dropped.  Without `out` a (B, Lout, Cout) tensor is allocated.  Returns `out`."""
+    ss = [_src1(s) for s in srcs]
+    for s in ss:
+        _check1d(s.t, "conv1d source")
+        if not s.t.is_contiguous() or s.t.dim() != 3 or s.t.shape[0] != ss[0].t.shape[0]:
+            raise RuntimeError(f"nps_hip conv1d: sources must be contiguous (B, L, C) of one batch, got {tuple(s.t.shape)}")
+    Cin = sum(s.t.shape[2] for s in ss)
+    if getattr(wpack, "nps_conv1d", None) != (Cout, Cin, K):
+        raise RuntimeError(f"nps_hip conv1d: the packing holds {getattr(wpack, 'nps_conv1d', None)}, the launch needs "
+                           f"(Cout, Cin, K) = {(Cout, Cin, K)}")
+    B, L = ss[0].t.shape[0], int(L)
+    pl, pr = (int(pad), int(pad)) if isinstance(pad, int) else (int(pad[0]), int(pad[1]))
+    Lout = (L + pl + pr - K) // stride + 1
+    if Lout <= 0:
+        raise RuntimeError(f"nps_hip conv1d: empty output for a frame of {L} padded by {(pl, pr)}, K={K}")
+    if out is None:
+        out = torch.empty((B, Lout, Cout), dtype=torch.float32, device=ss[0].t.device)
+    else:
+        _check1d(out, "conv1d out")
+        drop_stats(out)
+        drop_tag(out)
+    if not out.is_contiguous() or out.dim() != 3 or out.shape[0] != B or out.shape[2] < Cout:
+        raise RuntimeError(f"nps_hip conv1d: out must be contiguous (B, L, >= Cout), got {tuple(out.shape)}")
+    if addend is not None:
+        _check1d(addend, "conv1d addend")
+        if addend.shape != out.shape or not addend.is_contiguous():
+            raise RuntimeError("nps_hip conv1d: addend must be laid out like out")
+    if bias is not None:
+        _check1d(bias, "conv1d bias")
+        if bias.numel() != Cout or not bias.is_contiguous():
+            raise RuntimeError(f"nps_hip conv1d: bias must hold Cout = {Cout} contiguous values, got {tuple(bias.shape)}")
+    a = Conv1dArgs()
+    a.nsrc = len(ss)
+    for i, s in enumerate(ss):
+        a.src[i].ptr, a.src[i].C, a.src[i].L, a.src[i].off = ptr(s.t), s.t.shape[2], s.t.shape[1], s.off
+    a.B, a.Lc, a.Cin = B, L, Cin
+    a.K, a.stride, a.pad_l, a.pad_r, a.Lout = K, stride, pl, pr, Lout
+    a.wpack, a.bias, a.Cout = ptr(wpack), ptr(bias), Cout
+    a.out, a.out_C, a.out_L, a.out_os, a.out_off = ptr(out), out.shape[2], out.shape[1], out_os, int(out_off)
+    a.accumulate, a.addend, a.act = 1 if accumulate else 0, ptr(addend), act
+    if conv_probe is not None:
+        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        e0.record()
+        check(lib.nps_conv1d_fwd(ctypes_byref(a), stream_ptr()), "conv1d_fwd")
+        e1.record()
+        nbytes = 4.0 * (sum(s.t.numel() for s in ss) + Cout * Cin * K + B * Lout * Cout)
+        conv_probe.append((e0, e1, 2.0 * B * Lout * Cout * Cin * K, ("f32_1d", K, 4), nbytes))
+    else:
+        check(lib.nps_conv1d_fwd(ctypes_byref(a), stream_ptr()), "conv1d_fwd")
+    return out
+
+
+# ---- 1-D conv backward: the derived weights of the input gradients (torch ops on the parameter) and the weight gradient
+def conv1d_dgrad_weight(w: torch.Tensor) -> torch.Tensor:
+    """nn.Conv1d weight (Cout, Cin, K) -> the stride-1 input gradient's conv weight (Cin, Cout, K): taps flipped,
+    channels swapped.  dx = conv1d(dy, this) padded by (K - 1 - pad_l, K - 1 - pad_r)."""
+    return w.detach().flip(2).transpose(0, 1).contiguous()
+
+
+def conv_transpose1d_phase_weights(w: torch.Tensor) -> List[torch.Tensor]:
+    """nn.ConvTranspose1d weight (Cin, Cout, k <= 4) of a stride-2 transposed conv -> its two phases' 2-tap conv
+    weights (Cout, Cin, 2): output 2 q + r - padding = sum_t W_r[:, :, t] x[q + t - 1], W_r[co, ci, t] =
+    w[ci, co, 2 (1 - t) + r] (taps past k are zero)."""
+    w = w.detach()
+    if w.shape[2] < 4:
+        w = torch.nn.functional.pad(w, (0, 4 - w.shape[2]))
+    wt = w.transpose(0, 1)
+    return [torch.stack((wt[:, :, 2 + r], wt[:, :, r]), dim=2).contiguous() for r in (0, 1)]
+
+
+def _wgrad1d_args(a: torch.Tensor, x: torch.Tensor, K: int, stride: int, pad) -> Wgrad1dArgs:
+    for t in (a, x):
+        _check1d(t, "conv1d_wgrad tensor")
+        if t.dim() != 3 or not t.is_contiguous():
+            raise RuntimeError(f"nps_hip conv1d_wgrad: contiguous (B, L, C) tensors, got {tuple(t.shape)}")
+    if a.shape[0] != x.shape[0]:
+        raise RuntimeError("nps_hip conv1d_wgrad: a and x must share the batch")
+    p = Wgrad1dArgs()
+    p.a, (p.B, p.La, p.M) = ptr(a), a.shape
+    p.x, (_, p.Lx, p.N) = ptr(x), x.shape
+    p.K, p.stride = K, stride
+    p.pad_l, p.pad_r = (int(pad), int(pad)) if isinstance(pad, int) else (int(pad[0]), int(pad[1]))
+    return p
+
+
+def conv1d_wgrad(a: torch.Tensor, x: torch.Tensor, K: int, stride=1, pad=(0, 0)) -> torch.Tensor:
+    """g[M][N][K] = sum over a's positions of a[b][l][m] * xz[b][l*stride + t - pad_l][n] (nps_conv1d_wgrad, exact fp32
+    MFMA, fixed split schedule + reduce pass: run twice, the bits are the same): x (B, Lx, N) zero-extended, a
+    (B, La, M) of the K-tap / stride conv's output length over x padded by `pad`."""
+    p = _wgrad1d_args(a, x, K, stride, pad)
+    n = lib.nps_conv1d_wgrad_ws_floats(ctypes_byref(p))
+    if n == 0:
+        raise RuntimeError("conv1d_wgrad failed: " + lib.nps_last_error().decode())
+    ws = torch.empty(n, dtype=torch.float32, device=a.device)
+    g = torch.empty((p.M, p.N, K), dtype=torch.float32, device=a.device)
+    p.g, p.ws = ptr(g), ptr(ws)
+    check(lib.nps_conv1d_wgrad(ctypes_byref(p), stream_ptr()), "conv1d_wgrad")
+    return g
 
 
 # ------------------------------------------------------------------ data path -----
