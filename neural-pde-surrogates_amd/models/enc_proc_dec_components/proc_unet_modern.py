@@ -41,9 +41,14 @@ def _gn_args(norm_mod, stats):
     return ops.GN(stats, norm_mod.weight, norm_mod.bias, norm_mod.num_groups, float(norm_mod.eps))
 
 
+def _whole_frame(srcs, size):
+    """True when the frame is one source covering it (x itself, not a concatenation or a placed crop)."""
+    return len(srcs) == 1 and not any(srcs[0][1:]) and tuple(srcs[0].t.shape[1:1 + len(size)]) == tuple(size)
+
+
 def _check_identity_input(srcs, size):
-    """An identity shortcut adds x itself: one source that is the whole frame."""
-    if len(srcs) != 1 or any(srcs[0][1:]) or tuple(srcs[0].t.shape[1:1 + len(size)]) != tuple(size):
+    """The 3-D forms' identity shortcut adds x itself: one source that is the whole frame."""
+    if not _whole_frame(srcs, size):
         raise RuntimeError("identity shortcut on a concatenated input")
 
 
@@ -176,13 +181,22 @@ class UNetModern(nn.Module):
         if addend_fork is not None:
             addend_fork.join(addend)
         out = ops.empty_nhwc(B, Ht, Wt, self.final.out_channels, h)
-        if oy > 0 or ox > 0:
+        border = oy > 0 or ox > 0
+        if border:
             out.zero_()  # crop_Nd zero-pads when the output is smaller than the input
+        # the conv epilogue adds the addend and applies act_after only where it stores: with a zero-padded border
+        # (a single-resolution circular U-Net with a 3x3 final conv) the border must still become
+        # act_after(addend + 0), so that geometry takes the unfused add-then-activate of run_ad
+        unfused = border and addend is not None
         # the output carries its GroupNorm(1) moments (the next U-FNO block's norm1 frame reads it): no statistics
         # pass over it (zero crop padding adds nothing to the sums)
         st = ops.new_stats(B, out)
         self.final.run([ops.Src(h)], (H, W), gn=gn, pre_act=activation_code(self.activation), out=out,
-                       out_off=(oy, ox), addends=[addend] if addend is not None else [], act=act_after, out_stats=st)
+                       out_off=(oy, ox), addends=[addend] if addend is not None and not unfused else [],
+                       act=0 if unfused else act_after, out_stats=st)
+        if unfused:  # (a new tensor: it carries no moments, the next norm1 takes them in a statistics pass)
+            with torch.no_grad():
+                return ad.act(ad.add_at(addend, out), act_after)
         return ops.attach_stats(out, st)
 
     def run_ad(self, h, vb):
@@ -205,13 +219,23 @@ class UNetModern(nn.Module):
         if addend_fork is not None:
             addend_fork.join(addend)
         out = torch.empty(tuple(h_shape[:4]) + (self.final.out_channels,), dtype=h.dtype, device=h.device)
-        if any(o > 0 for o in off):
+        border = any(o > 0 for o in off)
+        if border:
             out.zero_()  # crop_Nd zero-pads when the output is smaller than the input
+        # as run(): a zero-padded border under a fused addend must become act_after(addend + 0), which the conv
+        # epilogue (it touches only what it stores) cannot give: the unfused add-then-activate of run_ad3d
+        unfused = border and addend is not None
+        if unfused and out.dtype != torch.float32:
+            raise NotImplementedError("UNetModern.run3d: a final conv smaller than its input under a fused addend "
+                                      "(single-resolution circular U-FNO, use1x1=False) runs in fp32 storage only")
         # the output's moments (the next U-FNO block's first norm1): those of the values the final conv stores
         # (after the addend and act_after; the crop border stays zero)
         st = ops.new_stats(out.shape[0], out) if ops.CARRY3D else None
         self.final.run3d([ops.Src3(h)], dhw, gn=gn, pre_act=activation_code(self.activation), out=out, out_off=off,
-                         addend=addend, act=act_after, out_stats=st)
+                         addend=None if unfused else addend, act=0 if unfused else act_after, out_stats=st)
+        if unfused:  # (a new tensor without moments: the next norm1 takes them in a statistics pass)
+            with torch.no_grad():
+                return ad.act(ad.add_at3d(addend, out), act_after)
         if st is not None:
             ops.attach_stats(out, st)
         return out
@@ -281,10 +305,15 @@ class ResidualBlock(nn.Module):
         st2 = out = None
         fork = None
         if isinstance(self.shortcut, nn.Identity):
-            _check_identity_input(srcs, frame_hw)
-            out = ops.share_tag(srcs[0].t.clone(), srcs[0].t)  # conv2 accumulates into it: same bound
+            if _whole_frame(srcs, frame_hw):
+                x = srcs[0].t
+                out = ops.share_tag(x.clone(), x)  # conv2 accumulates into it: same bound
+            else:
+                # in_channels (with the conditioning / skip channels) == out_channels: the identity adds the
+                # concatenation itself (e.g. hidden 16 + n_cond 16 -> 32), materialised once by nps_frame_pack
+                out = x = ops.frame_pack(srcs, frame_hw)
             if isinstance(self.norm1, nn.GroupNorm):
-                st2 = ops.copy_stats(ops.source_stats(srcs[0].t))
+                st2 = ops.copy_stats(ops.source_stats(x))
         else:
             # the 1x1 shortcut reads only x: it runs on a side stream beside conv1 (ops.Fork) when conv1's
             # persistent grid leaves many CUs idle in its last round (the 258^2 convs), its work-groups
@@ -355,14 +384,12 @@ class ResidualBlock(nn.Module):
         H, W = frame_hw
         n1 = self.norm1 if isinstance(self.norm1, nn.GroupNorm) else None
         n2 = self.norm2 if isinstance(self.norm2, nn.GroupNorm) else None
-        if isinstance(self.shortcut, nn.Identity):
-            _check_identity_input(srcs, frame_hw)
         # conv1's frame and the shortcut's input (x itself for the identity) from one node: the backward adds the
         # shortcut path's gradient inside the frame backward (ad.frame_pair), not as a separate accumulation
         f1, xin = ad.frame_pair(srcs, (H, W), n1, act) if ad.FRAME_PAIR else (ad.frame(srcs, (H, W), n1, act), None)
         h1 = self.conv1.run_ad(f1)
         if isinstance(self.shortcut, nn.Identity):
-            sc = xin if xin is not None else srcs[0].t
+            sc = xin if xin is not None else ad.frame(srcs, (H, W))  # (x itself, or the concatenation)
         else:
             sc = self.shortcut.run_ad(xin if xin is not None else ad.frame(srcs, (H, W)))
         h2 = self.conv2.run_ad(ad.frame([ops.Src(h1)], h1.shape[1:3], n2, act))

@@ -1,4 +1,5 @@
-"""Functional fp32 CPU restatement of the reference's hot-path modules (oracle).
+"""Functional CPU restatement of the reference's hot-path modules (oracle): fp32 as the reference runs it, and
+dtype-generic — on float64 / complex128 parameters and inputs it evaluates in fp64 (tests/unet2d_matrix.py).
 
 Test infrastructure only (see oracle/__init__.py).  Parameters come from a flat
 `state_dict` using the reference's own keys; `p` is the key prefix of the module.
@@ -77,7 +78,7 @@ def spectral_conv2d(x, w1, w2):
     m1, m2 = w1.shape[-2], w1.shape[-1]
     B = x.shape[0]
     x_ft = torch.fft.rfft2(x)
-    out_ft = torch.zeros(B, w1.shape[1], x.size(-2), x.size(-1) // 2 + 1, dtype=torch.cfloat)
+    out_ft = torch.zeros(B, w1.shape[1], x.size(-2), x.size(-1) // 2 + 1, dtype=x_ft.dtype)
     out_ft[:, :, :m1, :m2] = torch.einsum("bixy,ioxy->boxy", x_ft[:, :, :m1, :m2], w1)
     out_ft[:, :, -m1:, :m2] = torch.einsum("bixy,ioxy->boxy", x_ft[:, :, -m1:, :m2], w2)
     return torch.fft.irfft2(out_ft, s=(x.size(-2), x.size(-1)))
@@ -88,7 +89,7 @@ def spectral_conv3d(x, w1, w2, w3, w4):
     m1, m2, m3 = w1.shape[-3:]
     B = x.shape[0]
     x_ft = torch.fft.rfftn(x, dim=[-3, -2, -1])
-    out_ft = torch.zeros(B, w1.shape[1], x.size(-3), x.size(-2), x.size(-1) // 2 + 1, dtype=torch.cfloat)
+    out_ft = torch.zeros(B, w1.shape[1], x.size(-3), x.size(-2), x.size(-1) // 2 + 1, dtype=x_ft.dtype)
     mul = lambda a, w: torch.einsum("bixyz,ioxyz->boxyz", a, w)
     out_ft[:, :, :m1, :m2, :m3] = mul(x_ft[:, :, :m1, :m2, :m3], w1)
     out_ft[:, :, -m1:, :m2, :m3] = mul(x_ft[:, :, -m1:, :m2, :m3], w2)

@@ -111,3 +111,33 @@ def test_ufno3d_c5_volume_fp32_vs_oracle_and_bf16_vs_fp32():
     err = rel_l2(yb.cpu(), y32.cpu())
     print(f"C5 U-FNO 3D bf16 vs fp32 rel-L2 {err:.3e}")
     assert err < BF16_TOL
+
+
+def test_ufno3d_single_resolution_valid_final_conv_border():
+    """The 3-D twin of the 2-D matrix's border row (tests/unet2d_matrix.py UFNO_BORDER_ROW): ch_mults [1], circular,
+    use1x1=False.  The U-Net's final 3x3x3 conv is a valid conv, 2 smaller per axis than the block input, and crop_Nd
+    zero-pads it; the block output there is gelu(h_fno + 0), which the final conv's fused epilogue (it touches only
+    what it stores) cannot produce: run3d takes the unfused add-then-activate for that geometry.  Inference and
+    autograd forward against the fp64 oracle at the ufno3d_single golden's shape (8 x 10 x 12, hidden 8, n_cond 2),
+    GroupNorm affines and conv biases randomised."""
+    kw = dict(num_spatial_dims=3, n_cond=2, hidden_features=8, hidden_blocks=2, cond_mode="concat",
+              padding_mode="circular", fno_modes=(3, 4, 3), fno_kernel_size=1, fno_conv_mode="single", norm=True,
+              ch_mults=[1], is_attn=[False], mid_attn=False, n_blocks=1, use1x1=False)
+    m = _model("UFNO", kw, seed=7)
+    g = torch.Generator().manual_seed(8)
+    with torch.no_grad():
+        for k, p in m.named_parameters():
+            if ".norm" in k or k.endswith(".bias"):
+                u = torch.rand(p.shape, generator=g)
+                p.copy_((0.5 + u if k.endswith(".weight") else 0.6 * u - 0.3).to(DEV))
+    h = torch.rand(2, 8, 8, 10, 12, generator=g) * 2 - 1
+    vb = torch.rand(2, 2, 8, 10, 12, generator=g) * 2 - 1
+    f64 = lambda t: t.cpu().to(torch.complex128 if t.is_complex() else torch.float64)  # noqa: E731
+    with torch.no_grad():
+        ref = Fo.ufno3d({k: f64(v) for k, v in m.state_dict().items()}, "", kw, f64(h), f64(vb))
+        y = m(h.to(DEV), variables_broadcast=vb.to(DEV))
+    assert (ref[:, :, 0] != 0).any()  # (the border is not zero under a U-FNO)
+    y_ad = m(h.to(DEV), variables_broadcast=vb.to(DEV))
+    e, e_ad = rel_l2(y, ref), rel_l2(y_ad, ref)
+    print(f"3-D U-FNO border row: inference rel-L2 {e:.2e}, autograd form {e_ad:.2e}")
+    assert y_ad.requires_grad and e < TOL and e_ad < TOL
