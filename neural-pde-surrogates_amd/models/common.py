@@ -307,14 +307,8 @@ class Conv3d(_Packed3Mixin, _PackedMixin, nn.Conv3d):
             if use_autograd(self) and x.dtype == torch.float32:
                 return _ad_ncdhw(ad.conv3d, self, x)
             return run_form(self, x, None, lambda form, x, _: self.run3d([form.Src(x)], x.shape[1:4]))
-        B, C, D, H, W = x.shape
-        x4 = x.reshape(B, C, D * H, W)
-        if use_autograd(self):
-            y = ad.to_nchw(self.run_ad(ad.to_nhwc(x4)))
-        else:
-            x4 = ops.nchw_to_nhwc(x4)
-            y = ops.nhwc_to_nchw(self.run([ops.Src(x4)], (D * H, W)))
-        return y.reshape(B, self.out_channels, D, H, W)
+        return run_flat(self, x, None, lambda form, h, _, spatial: (
+            self.run_ad(h) if form is AUTOGRAD2D else self.run([ops.Src(h)], h.shape[1:3])))
 
 
 class Conv1d(_PackedMixin, nn.Conv1d):
@@ -455,14 +449,20 @@ def flat_frame(spatial):
     raise NotImplementedError(f"grids have 1 to 3 spatial axes, got {len(spatial)}")
 
 
-def run_pointwise(conv, x, **kw):
-    """conv.run on the one source x (B, rows, row, C) of a pointwise conv.  A Conv1d's 1 x L image folds into
-    32-point rows when L % 32 == 0 (as FNO_Layer.run folds its `w`: full conv tiles instead of 1/8 .. 1/32 used);
-    the output comes back in x's arrangement (planar with out_nchw=True, where the fold changes nothing)."""
-    B, R, L, _ = x.shape
-    if not (isinstance(conv, Conv1d) and R == 1 and L % 32 == 0 and L > 32):
-        return conv.run([ops.Src(x)], (R, L), **kw)
-    y = conv.run([ops.Src(ops.pixel_view(x, (B, L // 32, 32, x.shape[3])))], (L // 32, 32), **kw)
+def run_pointwise(conv, srcs, out=None, **kw):
+    """conv.run on the sources srcs (B, rows, row, C) of a pointwise conv (an FNO layer's (h | vb), an encoder's or
+    decoder's one tensor).  A Conv1d's 1 x L image folds into 32-point rows when L % 32 == 0, L > 32 and no source is
+    offset: a pointwise conv does not care how its pixels are arranged, and 32-point rows fill the 2-D conv tiles that
+    a 1 x L image would leave 1/8 .. 1/32 used.  `out` (to write or accumulate into) and the result are in the
+    sources' arrangement (planar with out_nchw=True, where the fold changes nothing)."""
+    B, R, L = srcs[0].t.shape[:3]
+    if not (isinstance(conv, Conv1d) and R == 1 and L % 32 == 0 and L > 32
+            and all(s.off_y == 0 and s.off_x == 0 for s in srcs)):
+        return conv.run(srcs, (R, L), out=out, **kw)
+    fold = lambda t: ops.pixel_view(t, (B, L // 32, 32, t.shape[3]))  # noqa: E731
+    y = conv.run([ops.Src(fold(s.t)) for s in srcs], (L // 32, 32), out=fold(out) if out is not None else None, **kw)
+    if out is not None:
+        return out
     return y.view(B, -1, 1, L) if kw.get("out_nchw") else ops.pixel_view(y, (B, 1, L, y.shape[3]))
 
 
@@ -569,3 +569,26 @@ def run_form(mod, x, vb, fn):
     vb = form.to_in(vb) if vb is not None else None
     y = fn(form, form.to_in(x), vb)
     return tuple(form.to_out(t) for t in y) if isinstance(y, tuple) else form.to_out(y)
+
+
+# bf16 storage (C5) of the 3-D FNO family's per-pixel layers: bf16 channels-last views through the fp32 transposes
+# (an fp32 conditioning next to bf16 activations is converted as fp32); inference only
+BF16FLAT = Form("run_bf16", ops.Src, 2, None,
+                lambda t: ops.to_bf16(ops.nchw_to_nhwc(ops.to_f32(t) if t.dtype == torch.bfloat16 else t.float())),
+                lambda y: ops.to_bf16(ops.nhwc_to_nchw(ops.to_f32(y))))
+
+
+def run_flat(mod, x, vb, fn, bf16=False):
+    """The module boundary of a per-pixel module's forward() (FNO layers, spectral and pointwise convs, and the U-FNO
+    whose U-Nets walk the same maps) at every grid rank: fn(form, h, vb, spatial) on the channels-last
+    (B, rows, row, C) views (flat_frame) of the (B, C, *spatial) tensor x and conditioning vb (or None), in the form
+    that the grad mode calls for (INFER2D / AUTOGRAD2D; BF16FLAT for a bf16 x of a module with a bf16-storage form,
+    `bf16`); the tensor it returns, as (B, C', *spatial)."""
+    spatial = tuple(x.shape[2:])
+    frame = flat_frame(spatial)
+    form = BF16FLAT if (bf16 and x.dtype == torch.bfloat16) else AUTOGRAD2D if use_autograd(mod) else INFER2D
+    # (a 2-D tensor goes in and comes out as it is: it keeps the range tag it carries)
+    flat = lambda t: t if spatial == frame else t.reshape(t.shape[:2] + frame)  # noqa: E731
+    vb = form.to_in(flat(vb)) if vb is not None else None
+    y = form.to_out(fn(form, form.to_in(flat(x)), vb, spatial))
+    return y if spatial == frame else y.reshape(y.shape[:2] + spatial)

@@ -166,20 +166,15 @@ class EncProcDec(ModelInterface):
                     layer._check_1d()  # fno_kernel_size > 1
 
     def _process(self, p, h, vb, spatial, train):
-        """One processor on h, vb in the flat-pixel frame of the grid, in the form it takes them."""
-        nd = len(spatial)
-        if nd == 2:
-            return p.run_ad(h, vb) if train else p.run(h, vb)
-        if isinstance(p, FNO):
-            kw = dict(D=spatial[0]) if nd == 3 else {}
-            return p.run_ad(h, vb, **kw) if train else p.run(h, vb, **kw)
-        if nd == 1:  # the 1-D U-Net / U-FNO walk the (B, 1, L, C) maps themselves
-            return p.run_ad(h, vb) if train else p.run(h, vb)
-        # the 3-D U-Net / U-FNO walk NDHWC volumes
-        ndhwc = lambda t: ops.pixel_view(t, (t.shape[0],) + tuple(spatial) + (t.shape[3],))  # noqa: E731
-        h5, vb5 = ndhwc(h), ndhwc(vb) if vb is not None else None
-        y = p.run_ad3d(h5, vb5) if train else p.run3d(h5, vb5)
-        return ops.pixel_view(y, tuple(h.shape[:3]) + (y.shape[4],))
+        """One processor on h, vb in the flat-pixel frame of the grid (common.flat_frame): run / run_ad(h, vb), with
+        the depth that the frame's rows fold away (an FNO's layers are per pixel: 3-D ones take (h, vb, D)); a
+        processor that walks volumes (run3d / run_ad3d of the 3-D U-Net / U-FNO) gets their NDHWC view."""
+        run = "run_ad" if train else "run"
+        if len(spatial) == 3 and hasattr(p, run + "3d"):
+            ndhwc = lambda t: ops.pixel_view(t, (t.shape[0],) + tuple(spatial) + (t.shape[3],))  # noqa: E731
+            y = getattr(p, run + "3d")(ndhwc(h), ndhwc(vb) if vb is not None else None)
+            return ops.pixel_view(y, tuple(h.shape[:3]) + (y.shape[4],))
+        return getattr(p, run)(h, vb, *spatial[:-2])
 
     def forward(self, x, cond=None, bc=None, pos=None, t_cond=None, spatial_cond=None):
         return self.forward_fused(x, cond=cond, bc=bc, pos=pos, t_cond=t_cond, spatial_cond=spatial_cond)

@@ -66,7 +66,7 @@ class TimeConvDense(nn.Module):
             raise NotImplementedError("TimeConvDense: dec_delta_mode='per_step' only on the MI355X path")
         if activation_code(self.decoder[1]) != ops.GELU:
             raise NotImplementedError("TimeConvDense: GELU activation only")
-        pre = run_pointwise(self.pre_decoder, h, out_nchw=True)
+        pre = run_pointwise(self.pre_decoder, [ops.Src(h)], out_nchw=True)
         c1, c2 = self.decoder[0], self.decoder[2]
         return ops.timeconv_decode(pre, u.contiguous(), c1.weight.detach().contiguous(), c1.bias.detach(),
                                    c2.weight.detach().contiguous(), c2.bias.detach(), self._dtcum(h.device), mask,

@@ -49,14 +49,14 @@ class ElementWise(nn.Module):
         c1, c2 = self.encoder[0], self.encoder[2]
         # xin carries <= 3 zero channels of padding; the packed weight is zero-padded to
         # 16-channel chunks, so the same packed buffer serves (ceil16(Cp) == ceil16(n_in)).
-        h = run_pointwise(c1, xin, act=act)
+        h = run_pointwise(c1, [ops.Src(xin)], act=act)
         if carry_stats is None:
             carry_stats = isinstance(c2, Conv2d)
         if not carry_stats:
-            return run_pointwise(c2, h, act=act)
+            return run_pointwise(c2, [ops.Src(h)], act=act)
         # the output carries its GroupNorm(1) moments (a U-Net processor's first norm reads it): no statistics pass
         st = ops.new_stats(h.shape[0], h)
-        return ops.attach_stats(run_pointwise(c2, h, act=act, out_stats=st), st)
+        return ops.attach_stats(run_pointwise(c2, [ops.Src(h)], act=act, out_stats=st), st)
 
     def run_packed_ad(self, xin):
         """Differentiable form of run_packed (the packed input is data: no gradient flows into it)."""

@@ -6,11 +6,14 @@ pipeline (nps_hip.ops.spectral_conv2d; 1-D: ops.spectral_conv1d).  Internal
 entry points `run(...)` take NHWC tensors / virtual frames so composite models
 never transpose.
 """
+from typing import Callable, NamedTuple
+
 import torch
 from torch import nn
 
 from common.interfaces import D, M
-from models.common import get_conv_with_right_spatial_dim, activation_code, use_autograd
+from models.common import (get_conv_with_right_spatial_dim, activation_code, use_autograd, run_flat, run_pointwise,
+                           AUTOGRAD2D, BF16FLAT)
 from nps_hip import ops
 from nps_hip import autograd as ad
 from pdes import PDE
@@ -59,22 +62,23 @@ class FNO(nn.Module):
                 "so FiLM is a module-level feature")
         return variables
 
+    def _layers(self, h, vb, step):
+        """The layer loop of run / run_ad / run_bf16: h = step(layer, srcs) on each layer's virtual input frame, (h | vb)
+        for cond_mode "concat"."""
+        for layer in self.fno_layers:
+            srcs = [ops.Src(h)] + ([ops.Src(vb)] if (vb is not None and self.cond_mode == "concat") else [])
+            h = step(layer, srcs)
+        return h
+
     def run(self, h, vb, D=None, variables=None):
         """NHWC: h (B,H,W,C), vb (B,H,W,K) or None (3-D: NDHWC viewed as (B, D*H, W, C), depth D; 1-D: channels-last
         (B, L, C) viewed as (B, 1, L, C)); variables (B, n_cond): the FiLM operand of cond_mode "film"."""
         p = self._film_p(variables)
-        for layer in self.fno_layers:
-            srcs = [ops.Src(h)] + ([ops.Src(vb)] if (vb is not None and self.cond_mode == "concat") else [])
-            h = layer.run(srcs, D=D) if self.num_spatial_dims == 3 else layer.run(srcs, p=p)
-        return h
+        return self._layers(h, vb, lambda layer, srcs: layer.run(srcs, D=D, p=p))
 
     def run_ad(self, h, vb, D=None, variables=None):
         p = self._film_p(variables)
-        for layer in self.fno_layers:
-            srcs = [ops.Src(h)] + ([ops.Src(vb)] if (vb is not None and self.cond_mode == "concat") else [])
-            x = ad.frame(srcs, h.shape[1:3])
-            h = layer.run_ad(x, D) if self.num_spatial_dims == 3 else layer.run_ad(x, p=p)
-        return h
+        return self._layers(h, vb, lambda layer, srcs: layer.run_ad(ad.frame(srcs, srcs[0].t.shape[1:3]), D, p))
 
     def run_bf16(self, h, vb, D):
         """bf16-storage forward of a 3-D FNO (BASELINE config C5): h (B, D*H, W, C), vb (B, D*H, W, K) bf16
@@ -83,47 +87,21 @@ class FNO(nn.Module):
             raise NotImplementedError("the bf16 storage path is the 3-D FNO's (config C5)")
         if self.cond_mode == "film":
             raise NotImplementedError("FiLM conditioning is not on the bf16 storage path")
-        for layer in self.fno_layers:
-            srcs = [ops.Src(h)] + ([ops.Src(vb)] if (vb is not None and self.cond_mode == "concat") else [])
-            h = layer.run_bf16(srcs, D)
-        return h
+        return self._layers(h, vb, lambda layer, srcs: layer.run_bf16(srcs, D))
 
     def forward(self, h: torch.Tensor, variables: torch.Tensor = None, variables_broadcast: torch.Tensor = None,
                 pos=None):
         self._film_p(variables)  # a FiLM FNO without `variables`, or in 3-D, raises before any work
-        if self.num_spatial_dims == 1:  # (B, C, L): the layers run on the (B, 1, L, C) view
-            for layer in self.fno_layers:
-                layer._check_1d()  # fno_kernel_size > 1 raises before any work
-            one = lambda t: t.unsqueeze(2) if t is not None else None
-            return self.forward2d(one(h), variables, one(variables_broadcast)).squeeze(2)
-        if self.num_spatial_dims == 3:  # (B, C, D, H, W): the layers run on the (B, D*H, W, C) view
-            B, C, D, H, W = h.shape
-            flat = lambda t: t.reshape(t.shape[0], t.shape[1], D * H, W)
-            if h.dtype == torch.bfloat16:  # bf16 storage (C5); inference only
-                if use_autograd(self):
-                    raise NotImplementedError("the bf16 3-D FNO path is inference-only (fp32 for training)")
-                # (an fp32 variables_broadcast next to bf16 h is converted as fp32)
-                tob = lambda t: ops.to_bf16(ops.nchw_to_nhwc(ops.to_f32(flat(t)) if t.dtype == torch.bfloat16
-                                                             else flat(t).float()))
-                vb = tob(variables_broadcast) if variables_broadcast is not None else None
-                y = ops.nhwc_to_nchw(ops.to_f32(self.run_bf16(tob(h), vb, D)))
-                return ops.to_bf16(y).reshape(B, y.shape[1], D, H, W)
-            if use_autograd(self):
-                vb = ad.to_nhwc(flat(variables_broadcast)) if variables_broadcast is not None else None
-                y = ad.to_nchw(self.run_ad(ad.to_nhwc(flat(h)), vb, D))
-            else:
-                vb = ops.nchw_to_nhwc(flat(variables_broadcast)) if variables_broadcast is not None else None
-                y = ops.nhwc_to_nchw(self.run(ops.nchw_to_nhwc(flat(h)), vb, D))
-            return y.reshape(B, y.shape[1], D, H, W)
-        return self.forward2d(h, variables, variables_broadcast)
+        rank = _RANKS[self.num_spatial_dims]
+        for layer in self.fno_layers:
+            rank.refuse_early(layer)  # (1-D: fno_kernel_size > 1)
+        if rank.bf16 and h.dtype == torch.bfloat16 and use_autograd(self):
+            raise NotImplementedError("the bf16 3-D FNO path is inference-only (fp32 for training)")
 
-    def forward2d(self, h, variables, variables_broadcast):
-        """(B, C, H, W) tensors through the NHWC layers (H = 1: the 1-D FNO's (B, C, 1, L) view)."""
-        if use_autograd(self):
-            vb = ad.to_nhwc(variables_broadcast) if variables_broadcast is not None else None
-            return ad.to_nchw(self.run_ad(ad.to_nhwc(h), vb, variables=variables))
-        vb = ops.nchw_to_nhwc(variables_broadcast) if variables_broadcast is not None else None
-        return ops.nhwc_to_nchw(self.run(ops.nchw_to_nhwc(h), vb, variables=variables))
+        def layers(form, h, vb, spatial):
+            kw = {} if form is BF16FLAT else dict(variables=variables)
+            return getattr(self, form.run)(h, vb, spatial[0] if rank.depth else None, **kw)
+        return run_flat(self, h, variables_broadcast, layers, bf16=rank.bf16)
 
 
 class FNO_Layer(nn.Module):
@@ -175,46 +153,25 @@ class FNO_Layer(nn.Module):
                                       "convs only)")
 
     def run(self, srcs, act_override=None, D=None, p=None):
-        """srcs: virtual NHWC input frame (h, vb) — for 3-D layers NDHWC sources viewed as (B, D*H, W, C); p (B, K):
-        the FiLM operand of a 1-D / 2-D layer with feature_transform (1-D layers: (B, 1, L, C) views).  Returns
+        """srcs: virtual NHWC input frame (h, vb) — for 3-D layers NDHWC sources viewed as (B, D*H, W, C), depth D; for
+        1-D layers (B, 1, L, C) views; p (B, K): the FiLM operand of a 1-D / 2-D layer with feature_transform.  Returns
         act(spectral(x) + w(x) [+ w2(x)])."""
-        if self.num_spatial_dims == 3:
-            DH, W = srcs[0].t.shape[1:3]
-            self._check_modes((D, DH // D, W))
-            if self.conv_mode != "single":
-                raise NotImplementedError("FNO_Layer 3-D: conv_mode 'single' only on the MI355X path")
-            act = activation_code(self.act) if act_override is None else act_override
-            out = self.w.run(srcs, (DH, W))
-            return self.conv.run(srcs, D, out=out, accumulate=True, act=act)
-        if self.num_spatial_dims == 1:
-            one, L = srcs[0].t.shape[1:3]
-            assert one == 1, "1-D layers take channels-last (B, L, C) sources viewed as (B, 1, L, C)"
-            self._check_modes((L,))
-            self._check_1d()
-            act = activation_code(self.act) if act_override is None else act_override
-            # a pointwise conv does not care how its pixels are arranged: 32-point rows fill the 2-D conv tiles that
-            # a 1 x L image would leave 1/8 .. 1/32 used
-            rows = L // 32 if (L % 32 == 0 and all(s.off_y == 0 and s.off_x == 0 for s in srcs)) else 1
-            fold = lambda t: ops.share_tag(t.view(t.shape[0], rows, L // rows, t.shape[3]), t)
-            psrcs = [ops.Src(fold(s.t)) for s in srcs] if rows > 1 else srcs
-            out = self.w.run(psrcs, (rows, L // rows))
-            if self.conv_mode == "double":
-                self.w2.run(psrcs, (rows, L // rows), out=out, accumulate=True)
-            out = out.view(out.shape[0], 1, L, out.shape[3])
-            return self.conv.run(srcs, out=out, accumulate=True, act=act, p=p)
+        rank = _RANKS[self.num_spatial_dims]
         H, W = srcs[0].t.shape[1:3]
-        self._check_modes((H, W))
+        self._check_modes(rank.spatial((H, W), D, "sources"))
+        rank.refuse(self)
         act = activation_code(self.act) if act_override is None else act_override
-        if self.conv_mode != "double" and ops.spectral_fusable(W, self.conv.modes2, self.conv.out_channels):
+        if (rank.fused and self.conv_mode != "double"
+                and ops.spectral_fusable(W, self.conv.modes2, self.conv.out_channels)):
             # conv(x) + w(x) in one output pass: the 1x1's epilogue synthesises the spectral conv's W pass
             # (nps_conv2d_t.spec_z; scale 1 / (H W) of irfft2's norm), then the activation.  FiLM acts on the mixed
             # modes, before Z is formed, so a FiLM layer takes the same route
             Z = self.conv.run_z(srcs, p=p)
             return self.w.run(srcs, (H, W), spec=(Z, self.conv.modes2, 1.0 / (H * W)), act=act)
-        out = self.w.run(srcs, (H, W))
+        out = run_pointwise(self.w, srcs)  # (a 1-D layer's pixels fold into 32-point rows)
         if self.conv_mode == "double":
-            self.w2.run(srcs, (H, W), out=out, accumulate=True)
-        return self.conv.run(srcs, out=out, accumulate=True, act=act, p=p)
+            run_pointwise(self.w2, srcs, out=out, accumulate=True)
+        return self.conv.run(srcs, out=out, accumulate=True, act=act, p=p, D=D)
 
     def run_bf16(self, srcs, D, act_override=None):
         """3-D layer in bf16 storage: act(spectral(x) + w(x)) with bf16 sources / output, fp32 sums."""
@@ -227,51 +184,56 @@ class FNO_Layer(nn.Module):
         return self.conv.run_bf16(srcs, D, out=out, accumulate=True, act=act)
 
     def run_ad(self, x, D=None, p=None):
-        """Differentiable form: x (B,H,W,Cin) materialised frame ((B, D*H, W, Cin) for 3-D layers); p as in run."""
-        if self.num_spatial_dims == 3:
-            DH, W = x.shape[1:3]
-            self._check_modes((D, DH // D, W))
-            if self.conv_mode != "single":
-                raise NotImplementedError("FNO_Layer 3-D: conv_mode 'single' only on the MI355X path")
-            y = ad.add_at(ad.spectral_conv3d(self.conv, x, D), self.w.run_ad(x))
-            return ad.act(y, activation_code(self.act))
-        if self.num_spatial_dims == 1:
-            assert x.shape[1] == 1, "1-D layers take channels-last (B, L, C) tensors viewed as (B, 1, L, C)"
-            self._check_modes(x.shape[2:3])
-            self._check_1d()
-            spec = (ad.spectral_conv1d_film(self.conv, x, p) if self.conv.feature_transform
-                    else ad.spectral_conv1d(self.conv, x))
-            y = ad.add_at(spec, self.w.run_ad(x))
-            if self.conv_mode == "double":
-                y = ad.add_at(y, self.w2.run_ad(x))
-            return ad.act(y, activation_code(self.act))
-        self._check_modes(x.shape[1:3])
-        spec = (ad.spectral_conv2d_film(self.conv, x, p) if self.conv.feature_transform
-                else ad.spectral_conv2d(self.conv, x))
-        y = ad.add_at(spec, ad.conv2d(self.w, x))
+        """Differentiable form: x (B,H,W,Cin) materialised frame ((B, D*H, W, Cin) for 3-D layers, (B, 1, L, Cin) for
+        1-D ones); p as in run."""
+        rank = _RANKS[self.num_spatial_dims]
+        self._check_modes(rank.spatial(tuple(x.shape[1:3]), D, "tensors"))
+        rank.refuse(self)
+        y = ad.add_at(self.conv.run_ad(x, p=p, D=D), self.w.run_ad(x))
         if self.conv_mode == "double":
-            y = ad.add_at(y, ad.conv2d(self.w2, x))
+            y = ad.add_at(y, self.w2.run_ad(x))
         return ad.act(y, activation_code(self.act))
 
     def forward(self, x, p=None):
-        if self.num_spatial_dims == 3:
-            if self.conv.feature_transform:
-                raise NotImplementedError(SpectralConv3d.FILM_MSG)
-            B, C, D, H, W = x.shape
-            x4 = x.reshape(B, C, D * H, W)
-            if use_autograd(self):
-                y = ad.to_nchw(self.run_ad(ad.to_nhwc(x4), D))
-            else:
-                y = ops.nhwc_to_nchw(self.run([ops.Src(ops.nchw_to_nhwc(x4))], D=D))
-            return y.reshape(B, y.shape[1], D, H, W)
-        if self.num_spatial_dims == 1:  # (B, C, L) as (B, C, 1, L)
-            self._check_1d()
-            x = x.unsqueeze(2)
-        if use_autograd(self):
-            y = ad.to_nchw(self.run_ad(ad.to_nhwc(x), p=p))
-        else:
-            y = ops.nhwc_to_nchw(self.run([ops.Src(ops.nchw_to_nhwc(x))], p=p))
-        return y.squeeze(2) if self.num_spatial_dims == 1 else y
+        rank = _RANKS[self.num_spatial_dims]
+        rank.refuse_early(self)
+
+        def layer(form, h, _, spatial):
+            D = spatial[0] if rank.depth else None
+            return self.run_ad(h, D, p) if form is AUTOGRAD2D else self.run([ops.Src(h)], D=D, p=p)
+        return run_flat(self, x, None, layer)
+
+
+def _line(hw, D, what):
+    assert hw[0] == 1, f"1-D layers take channels-last (B, L, C) {what} viewed as (B, 1, L, C)"
+    return hw[1:]
+
+
+def _refuse_double(layer):
+    if layer.conv_mode != "single":
+        raise NotImplementedError("FNO_Layer 3-D: conv_mode 'single' only on the MI355X path")
+
+
+def _refuse_film(layer):
+    if layer.conv.feature_transform:
+        raise NotImplementedError(SpectralConv3d.FILM_MSG)
+
+
+class _Rank(NamedTuple):
+    """What differs between the grid ranks in the one run / run_ad / forward body of an FNO layer."""
+    spatial: Callable       # ((rows, row) of the flat frame, D, what the caller passed) -> the grid's sizes (_check_modes)
+    refuse: Callable        # layer -> raises what run / run_ad refuse at this rank, after the modes check
+    refuse_early: Callable  # layer -> raises what forward() refuses before its layout transposes
+    depth: bool = False     # a depth D accompanies the (D*H, W) frame
+    fused: bool = False     # the `w` conv can take the spectral conv's W pass (ops.spectral_fusable)
+    bf16: bool = False      # the FNO has a bf16-storage form
+
+
+_RANKS = {
+    1: _Rank(_line, FNO_Layer._check_1d, FNO_Layer._check_1d),
+    2: _Rank(lambda hw, D, what: hw, lambda layer: None, lambda layer: None, fused=True),
+    3: _Rank(lambda hw, D, what: (D, hw[0] // D, hw[1]), _refuse_double, _refuse_film, depth=True, bf16=True),
+}
 
 
 def _film(conv, p):
@@ -312,10 +274,15 @@ class SpectralConv2d(nn.Module):
             self._pk_key = key
         return self._pk
 
-    def run(self, srcs, out=None, accumulate=False, addend=None, act=0, p=None):
+    def run(self, srcs, out=None, accumulate=False, addend=None, act=0, p=None, D=None):
+        """srcs: NHWC sources.  Returns (B, H, W, Cout), or `out`.  (D: the depth a 3-D layer passes; none here.)"""
         H = srcs[0].t.shape[1]
         return ops.spectral_conv2d(srcs, self.packed(H), self.modes1, self.modes2, self.out_channels, out=out,
                                    accumulate=accumulate, addend=addend, act=act, film=_film(self, p))
+
+    def run_ad(self, x, p=None, D=None):
+        """Differentiable form on an NHWC tensor."""
+        return ad.spectral_conv2d_film(self, x, p) if self.feature_transform else ad.spectral_conv2d(self, x)
 
     def run_z(self, srcs, p=None):
         """The spectrum Z (B, H, m2, Cout) before the W-pass synthesis (ops.spectral_z): the FNO layer hands it to
@@ -359,24 +326,21 @@ class SpectralConv1d(nn.Module):
             self._pk_key = key
         return self._pk
 
-    def run(self, srcs, out=None, accumulate=False, addend=None, act=0, p=None):
+    def run(self, srcs, out=None, accumulate=False, addend=None, act=0, p=None, D=None):
         """srcs: channels-last (B, L, C) sources, or their (B, 1, L, C) views.  Returns (B, L, Cout), or `out`."""
         return ops.spectral_conv1d(srcs, self.packed(), self.modes1, self.out_channels, out=out,
                                    accumulate=accumulate, addend=addend, act=act, film=_film(self, p))
 
-    def run_ad(self, x, p=None):
+    def run_ad(self, x, p=None, D=None):
         """Differentiable form on a channels-last (B, L, Cin) tensor (or its (B, 1, L, Cin) view)."""
         return ad.spectral_conv1d_film(self, x, p) if self.feature_transform else ad.spectral_conv1d(self, x)
 
     def forward(self, x, p=None):
-        film = _film(self, p)
-        L = x.shape[2]  # x (B, C, L), transposed on the (B, C, 1, L) view by the layout kernels
-        ops.check_modes1d(L, self.modes1)
-        if use_autograd(self):
-            return ad.to_nchw(self.run_ad(ad.to_nhwc(x.unsqueeze(2)), p)).squeeze(2)
-        y = ops.spectral_conv1d([ops.Src(ops.nchw_to_nhwc(x.unsqueeze(2)))], self.packed(), self.modes1,
-                                self.out_channels, film=film)
-        return ops.nhwc_to_nchw(y.unsqueeze(1)).squeeze(2)
+        _film(self, p)  # feature_transform without p
+        ops.check_modes1d(x.shape[2], self.modes1)
+        # x (B, C, L) is transposed on its (B, C, 1, L) view; the inference form hands back (B, L, Cout)
+        return run_flat(self, x, None, lambda form, h, _, spatial: (
+            self.run_ad(h, p) if form is AUTOGRAD2D else self.run([ops.Src(h)], p=p).unsqueeze(1)))
 
 
 class SpectralConv3d(nn.Module):
@@ -427,13 +391,18 @@ class SpectralConv3d(nn.Module):
         return ops.spectral_conv3d_bf16(srcs, D, self.packed_bf16(D, H), self.modes1, self.modes2, self.modes3,
                                         self.out_channels, out=out, accumulate=accumulate, addend=addend, act=act)
 
-    def run(self, srcs, D, out=None, accumulate=False, addend=None, act=0):
-        """srcs: NDHWC sources viewed as (B, D*H, W, C).  Returns (B, D*H, W, Cout)."""
+    def run(self, srcs, D=None, out=None, accumulate=False, addend=None, act=0, p=None):
+        """srcs: NDHWC sources viewed as (B, D*H, W, C), depth D.  Returns (B, D*H, W, Cout).  (p: the FiLM operand
+        a layer passes; FiLM is refused here.)"""
         if self.feature_transform:
             raise NotImplementedError(self.FILM_MSG)
         H = srcs[0].t.shape[1] // D
         return ops.spectral_conv3d(srcs, D, self.packed(D, H), self.modes1, self.modes2, self.modes3,
                                    self.out_channels, out=out, accumulate=accumulate, addend=addend, act=act)
+
+    def run_ad(self, x, p=None, D=None):
+        """Differentiable form on the (B, D*H, W, Cin) view of an NDHWC tensor, depth D."""
+        return ad.spectral_conv3d(self, x, D)
 
     def forward(self, x, p=None):
         if self.feature_transform:
@@ -441,10 +410,7 @@ class SpectralConv3d(nn.Module):
         B, C, D, H, W = x.shape
         ops.check_modes3d(D, H, W, self.modes1, self.modes2, self.modes3)
         if x.dtype == torch.bfloat16:  # bf16 storage (C5), inference only
-            x4 = x.reshape(B, C, D * H, W)
-            xb = ops.to_bf16(ops.nchw_to_nhwc(ops.to_f32(x4.contiguous())))
-            y = ops.nhwc_to_nchw(ops.to_f32(self.run_bf16([ops.Src(xb)], D)))
-            return ops.to_bf16(y).reshape(B, self.out_channels, D, H, W)
+            return run_flat(self, x, None, lambda form, h, _, spatial: self.run_bf16([ops.Src(h)], D), bf16=True)
         # fp32: the module's own NCDHW tensors go straight to the channels-first W passes
         if use_autograd(self):
             return ad.spectral_conv3d_nchw(self, x)
