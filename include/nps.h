@@ -621,6 +621,60 @@ int nps_volume_rescale_bwd(const float* g, const double* new_tot, const double* 
                            const float* mask, int mask_S, int mask_ch, const double* D, float* gu, int B, int num_c,
                            int tw, int H, int W, void* stream);
 
+/* ---- grid decoders: the per-pixel Conv1d chain + add_delta + tanh + mask (csrc/decode_chain.hip) ----
+ * One entry for dec_grid.TimeConvLinear (one stage), TimeConv and TimeConvDense with dec_delta_mode 'all' / 'none'
+ * (two stages), and LinearConv's epilogue / add_delta itself (no stage); dec_grid.py:8-31, :34-195.
+ * TimeConvDense with 'per_step' and GELU stays on nps_timeconv_decode.
+ *
+ * Input: a pixel's signal x[ci][l], ci < C0, l < L0, at x[b * x_bs + pix * x_ps + (ci * L0 + l) * x_cs] (element
+ * strides): the planar [B][C0*L0][N] is (C0*L0*N, 1, N), channels-last [B][N][C0*L0] is (N*C0*L0, C0*L0, 1).
+ * N is the flat pixel count of a 1-D, 2-D or 3-D grid.
+ * Stage 1 (nstage >= 1): Conv1d(C0 -> C1, k1, stride s1 >= 1), w1 [C1][C0][k1], b1 [C1]; L1 = (L0 - k1) / s1 + 1; then
+ * `act` (NPS_DECODE_ACT_*; Swish is z * sigmoid(beta z)).  Stage 2 (nstage == 2): Conv1d(C1 -> C2, k2, stride 1),
+ * w2 [C2][C1][k2], b2 [C2].  The last stage must yield exactly num_c channels x tw positions (nstage == 0:
+ * C0 * L0 == num_c * tw); anything else is refused with the sizes in nps_last_error().
+ * Epilogue on the chain's output d[c][t]: delta_mode NPS_DECODE_PER_STEP u_last + dtcum[t] * d (dtcum: tw floats, the
+ * fp32 cumsum of dt), NPS_DECODE_ALL u_last + dt * d, NPS_DECODE_NONE d; u_last = u[b][c][tw - 1][pix] of the model
+ * input u (B, num_c, tw, N) (dec_delta_dt=False is dt = 1 on the caller's side); then tanh when act_tanh; then
+ * v - m * v with m = mask[b][mask_ch][pix] of mask (B, mask_S, N), or no mask when NULL.  out: (B, num_c, tw, N).
+ * LDS: the kernels keep 64, 32, 16 or 8 pixels' arrays per work-group, the most that fit 160 KiB; a chain whose 8
+ * pixels do not fit is refused. */
+enum { NPS_DECODE_ACT_NONE = 0, NPS_DECODE_ACT_GELU = 1, NPS_DECODE_ACT_SWISH = 2 };
+enum { NPS_DECODE_PER_STEP = 0, NPS_DECODE_ALL = 1, NPS_DECODE_NONE = 2 };
+typedef struct {
+    const float* x;
+    long x_bs, x_ps, x_cs;
+    int B, N;
+    int nstage;
+    int C0, L0;
+    int C1, k1, s1;
+    int act;
+    float beta;
+    int C2, k2;
+    const float* w1;
+    const float* b1;
+    const float* w2;
+    const float* b2;
+    const float* u;
+    int num_c, tw;
+    int delta_mode;
+    float dt;
+    const float* dtcum;
+    int act_tanh;
+    const float* mask;
+    int mask_S, mask_ch;
+    float* out;
+} nps_decode_t;
+int nps_decode_fwd(const nps_decode_t* d, void* stream);
+/* Backward given gout = dL/d(out) (B, num_c, tw, N): gx in x's strided layout (d->out is not read), gw1 / gb1 / gw2 /
+ * gb2 shaped like the parameters; u gets no gradient.  A NULL pointer skips that gradient.  Parameter gradients need
+ * ws, nps_decode_bwd_ws_floats(d) floats: at most 1024 work-groups walk the pixel groups, each sums its
+ * (parameter, group) terms (an fp64 wave reduction over a group's pixels) into its own row of ws, and a second kernel
+ * adds the rows in a fixed order.  There are no atomics: two runs on the same inputs give identical bits. */
+size_t nps_decode_bwd_ws_floats(const nps_decode_t* d);
+int nps_decode_bwd(const nps_decode_t* d, const float* gout, float* gx, float* gw1, float* gb1, float* gw2,
+                   float* gb2, float* ws, void* stream);
+
 /* ---- 3-D U-Net of the 3-D U-FNO (BASELINE config C5: U-FNO 3D over a time-bundled D x H x W volume) ----
  * The reference builds the 3-D U-Net's ResidualBlock / Down / Middle / Downsample from nn.Conv3d and
  * nn.GroupNorm (proc_unet_modern.py:199-455 with num_spatial_dims=3) but has no 3-D Upsample

@@ -22,14 +22,16 @@ def use_autograd(module) -> bool:
 
 
 class Swish(nn.Module):
-    """common.py:7-17 (unused by the twophase cfgs, which pass GELU)."""
+    """common.py:7-17: x * sigmoid(beta x).  The one place the models use it, dec_grid.TimeConv's chain, applies it
+    inside the decode kernel (NPS_DECODE_ACT_SWISH with this beta); forward is the same function in torch ops, on
+    whatever tensor it is given."""
 
     def __init__(self, beta=1):
         super().__init__()
         self.beta = beta
 
     def forward(self, x):
-        raise NotImplementedError("Swish is not on the MI355X hot path (twophase cfgs use GELU)")
+        return x * torch.sigmoid(self.beta * x)
 
 
 def activation_code(act):

@@ -13,7 +13,7 @@ import os
 
 import torch
 
-__all__ = ["lib", "Src", "Conv2dArgs", "WgradArgs", "Wgrad3dArgs", "Src3", "Conv3dArgs", "Src1", "Conv1dArgs", "Wgrad1dArgs", "PackJob", "check", "stream_ptr", "ptr", "LIB_PATH"]
+__all__ = ["lib", "Src", "Conv2dArgs", "WgradArgs", "Wgrad3dArgs", "Src3", "Conv3dArgs", "Src1", "Conv1dArgs", "Wgrad1dArgs", "DecodeArgs", "PackJob", "check", "stream_ptr", "ptr", "LIB_PATH"]
 
 LIB_PATH = os.environ.get("NPS_HIP_LIB", os.path.join(os.path.dirname(os.path.abspath(__file__)), "libnps_hip.so"))
 if not os.path.exists(LIB_PATH):
@@ -124,6 +124,19 @@ class Wgrad1dArgs(ctypes.Structure):
     ]
 
 
+class DecodeArgs(ctypes.Structure):
+    _fields_ = [
+        ("x", ctypes.c_void_p), ("x_bs", ctypes.c_long), ("x_ps", ctypes.c_long), ("x_cs", ctypes.c_long),
+        ("B", ctypes.c_int), ("N", ctypes.c_int), ("nstage", ctypes.c_int), ("C0", ctypes.c_int), ("L0", ctypes.c_int),
+        ("C1", ctypes.c_int), ("k1", ctypes.c_int), ("s1", ctypes.c_int), ("act", ctypes.c_int),
+        ("beta", ctypes.c_float), ("C2", ctypes.c_int), ("k2", ctypes.c_int),
+        ("w1", ctypes.c_void_p), ("b1", ctypes.c_void_p), ("w2", ctypes.c_void_p), ("b2", ctypes.c_void_p),
+        ("u", ctypes.c_void_p), ("num_c", ctypes.c_int), ("tw", ctypes.c_int), ("delta_mode", ctypes.c_int),
+        ("dt", ctypes.c_float), ("dtcum", ctypes.c_void_p), ("act_tanh", ctypes.c_int), ("mask", ctypes.c_void_p),
+        ("mask_S", ctypes.c_int), ("mask_ch", ctypes.c_int), ("out", ctypes.c_void_p),
+    ]
+
+
 _vp, _i, _l, _sz = ctypes.c_void_p, ctypes.c_int, ctypes.c_long, ctypes.c_size_t
 _SIGS = {
     "nps_conv2d_packed_size": (_sz, [_i, _i, _i]),
@@ -188,6 +201,9 @@ _SIGS = {
     "nps_spectral3d_unpack_grad": (_i, [_vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _i, _vp]),
     "nps_timeconv_decode_bwd": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _vp, _vp, _vp, _i, _i, _i, _i,
                                      _i, _i, _vp]),
+    "nps_decode_fwd": (_i, [ctypes.POINTER(DecodeArgs), _vp]),
+    "nps_decode_bwd_ws_floats": (_sz, [ctypes.POINTER(DecodeArgs)]),
+    "nps_decode_bwd": (_i, [ctypes.POINTER(DecodeArgs)] + [_vp] * 8),
     "nps_plane_dot": (_i, [_vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _vp, _vp]),
     "nps_volume_rescale_bwd": (_i, [_vp, _vp, _vp, _vp, _vp, _i, _i, _vp, _vp, _i, _i, _i, _i, _i, _vp]),
     # one call per module (composites of the spectral stages)

@@ -1253,6 +1253,39 @@ class TimeConvDecodeFn(torch.autograd.Function):
         return None, gpre, None, gw1, gb1, gw2, gb2, None, None
 
 
+class DecodeChainFn(torch.autograd.Function):
+    """ops.decode_chain (the per-pixel Conv1d chain of the grid decoders + add_delta + tanh + mask) and its HIP
+    backward nps_decode_bwd: gradients of x (in x's layout) and of the stages' weights and biases; u is data."""
+
+    @staticmethod
+    def forward(ctx, spec, x, u, w1, b1, w2, b2, dtcum, mask):
+        x, u = _c(x), _c(u)
+        ws = [None if w is None else w.detach().contiguous() for w in (w1, b1, w2, b2)]
+        out = ops.decode_chain(spec, x, u, *ws, dtcum, mask)
+        ctx.spec = spec
+        ctx.present = [t is not None for t in (w1, b1, w2, b2, dtcum, mask)]
+        ctx.save_for_backward(x, u, *[t for t in (w1, b1, w2, b2, dtcum, mask) if t is not None])
+        return out
+
+    @staticmethod
+    def backward(ctx, gout):
+        x, u = ctx.saved_tensors[:2]
+        rest = list(ctx.saved_tensors[2:])
+        w1, b1, w2, b2, dtcum, mask = [rest.pop(0) if have else None for have in ctx.present]
+        ws = [None if w is None else w.detach().contiguous() for w in (w1, b1, w2, b2)]
+        gout = _c(gout)
+        d = ops.decode_args(ctx.spec, x, u, *ws, dtcum, mask)
+        need = ctx.needs_input_grad
+        gx = torch.empty_like(x) if need[1] else None
+        gp = [torch.empty_like(w) if (w is not None and need[3 + i]) else None for i, w in enumerate(ws)]
+        work = None
+        if any(g is not None for g in gp):
+            work = torch.empty(lib.nps_decode_bwd_ws_floats(ctypes.byref(d)), dtype=torch.float32, device=x.device)
+        check(lib.nps_decode_bwd(ctypes.byref(d), ptr(gout), ptr(gx), ptr(gp[0]), ptr(gp[1]), ptr(gp[2]), ptr(gp[3]),
+                                 ptr(work), stream_ptr()), "decode_chain_bwd")
+        return None, gx, None, gp[0], gp[1], gp[2], gp[3], None, None
+
+
 class VolumeRescaleFn(torch.autograd.Function):
     """activation_wrapper 'individual_static' volume preservation + re-applied mask
     (activation_wrapper.py:80-105); x (the model input) is data and gets no gradient."""

@@ -13,7 +13,7 @@ from typing import List, NamedTuple, Optional, Sequence, Union
 
 import torch
 
-from . import Conv1dArgs, Conv2dArgs, Conv3dArgs, PackJob, Wgrad1dArgs, Wgrad3dArgs, Src as _CSrc, Src3 as _CSrc3, check, lib, ptr, stream_ptr
+from . import Conv1dArgs, Conv2dArgs, Conv3dArgs, DecodeArgs, PackJob, Wgrad1dArgs, Wgrad3dArgs, Src as _CSrc, Src3 as _CSrc3, check, lib, ptr, stream_ptr
 
 GELU = 1
 
@@ -1754,6 +1754,67 @@ def timeconv_decode(pre, u, w1, b1, w2, b2, dtcum, mask, mask_ch, act_tanh, num_
     check(lib.nps_timeconv_decode(ptr(pre), ptr(u), ptr(w1), ptr(b1), ptr(w2), ptr(b2), ptr(dtcum), ptr(mask), S,
                                   mask_ch, ptr(out), B, num_c, tw, 1, N, 1 if act_tanh else 0, stream_ptr()),
           "timeconv_decode")
+    return out
+
+
+# the grid decoders' per-pixel chain (include/nps.h nps_decode_t)
+DECODE_ACT_NONE, DECODE_ACT_GELU, DECODE_ACT_SWISH = 0, 1, 2
+DELTA_MODES = {"per_step": 0, "all": 1, "none": 2}  # dec_grid.py:11
+
+
+class DecodeSpec(NamedTuple):
+    """The constants of one decode chain: the layout of its input (planar (B, C0*L0, N) or channels-last
+    (B, N, C0*L0), in any view), stage 1's stride and activation, and the epilogue."""
+    planar: bool
+    C0: int
+    L0: int
+    num_c: int
+    tw: int
+    delta_mode: int = 0     # DELTA_MODES
+    dt: float = 1.0         # 'all'
+    s1: int = 1
+    act: int = 0            # DECODE_ACT_*
+    beta: float = 1.0       # Swish
+    act_tanh: bool = False
+    mask_ch: int = 0
+
+
+def decode_args(spec: DecodeSpec, x, u, w1, b1, w2, b2, dtcum, mask, out=None) -> DecodeArgs:
+    """nps_decode_t of a chain on x with the stages that have weights (w1 (C1, C0, k1) or None, w2 (C2, C1, k2) or
+    None); u is the model input (B, num_c, tw, *spatial)."""
+    B, N = u.shape[0], grid_pixels(u)
+    CL = spec.C0 * spec.L0
+    if x.numel() != B * N * CL or not x.is_contiguous() or x.dtype != torch.float32:
+        raise RuntimeError(f"decode_chain: x {tuple(x.shape)} is not a contiguous fp32 tensor of B={B} x N={N} pixels "
+                           f"x C0*L0={spec.C0}*{spec.L0}")
+    if w2 is not None and w1 is None:
+        raise RuntimeError("decode_chain: a second stage needs a first")
+    d = DecodeArgs()
+    d.x = ptr(x)
+    d.x_bs, d.x_ps, d.x_cs = (CL * N, 1, N) if spec.planar else (N * CL, CL, 1)
+    d.B, d.N, d.C0, d.L0 = B, N, spec.C0, spec.L0
+    d.nstage = (w1 is not None) + (w2 is not None)
+    if w1 is not None:
+        d.C1, d.k1, d.s1, d.act, d.beta = w1.shape[0], w1.shape[2], spec.s1, spec.act, float(spec.beta)
+        d.w1, d.b1 = ptr(w1), ptr(b1)
+    if w2 is not None:
+        d.C2, d.k2 = w2.shape[0], w2.shape[2]
+        d.w2, d.b2 = ptr(w2), ptr(b2)
+    d.u, d.num_c, d.tw = ptr(u), spec.num_c, spec.tw
+    d.delta_mode, d.dt, d.dtcum = spec.delta_mode, float(spec.dt), ptr(dtcum)
+    d.act_tanh = 1 if spec.act_tanh else 0
+    if mask is not None:
+        d.mask, d.mask_S, d.mask_ch = ptr(mask), mask.shape[1], spec.mask_ch
+    d.out = ptr(out)
+    return d
+
+
+def decode_chain(spec: DecodeSpec, x, u, w1=None, b1=None, w2=None, b2=None, dtcum=None, mask=None):
+    """The decoders' per-pixel chain on HIP (nps_decode_fwd): up to two Conv1d stages over each pixel's signal in x,
+    add_delta in the mode of spec, tanh and the spatial-cond mask -> (B, num_c, tw, *spatial)."""
+    out = torch.empty((u.shape[0], spec.num_c, spec.tw) + tuple(u.shape[3:]), dtype=torch.float32, device=u.device)
+    d = decode_args(spec, x, u, w1, b1, w2, b2, dtcum, mask, out)
+    check(lib.nps_decode_fwd(ctypes.byref(d), stream_ptr()), "decode_chain")
     return out
 
 
