@@ -621,6 +621,32 @@ int nps_volume_rescale_bwd(const float* g, const double* new_tot, const double* 
                            const float* mask, int mask_S, int mask_ch, const double* D, float* gu, int B, int num_c,
                            int tw, int H, int W, void* stream);
 
+/* ---- approx_volume_preserve 'block' and 'individual' (csrc/volume.hip; activation_wrapper.py:40-79) ----
+ * With s_t = sum_hw u[b,c,t] and p = sum_hw x[b,c,-1] (new_tot[B*c*tw], prev_tot[B*c]: nps_plane_sums), m =
+ * max_pct_dif and r(s, p) = 1 - tanh((1 - s / p) 100 / m) m / 100, every mode is out[b,c,t] = u[b,c,t] F[b,c,t],
+ * then out -= mask out.  The factor entries run one thread per (b, c) over the time window with every scalar in
+ * fp64 and write one fp32 value per plane; the apply entries are the fp32 element-wise passes.  All four refuse null
+ * pointers, non-positive extents, more than 65535 planes, an unknown mode and an m that is not finite and positive. */
+#define NPS_VOLUME_BLOCK 0
+#define NPS_VOLUME_INDIVIDUAL 1
+/* F[B*c*tw].  block: Sm = mean_t s_t, F_t = p r(Sm, p) / Sm for every t.
+ * individual: p_0 = p, r_i = r(s_i, p_i), F_i = r_i p_i / s_i, p_{i+1} = r_i p_i. */
+int nps_volume_factors(const double* new_tot, const double* prev_tot, int mode, double max_pct_dif, float* F, int B,
+                       int num_c, int tw, void* stream);
+/* c[B*c*tw], c_t = sum_t' D_t' dF_t'/ds_t with D[B*c*tw] = sum_hw g (1 - mask) u (nps_plane_dot).
+ * block: th = tanh((1 - Sm / p) 100 / m), c_t = (sum_t' D_t') ((1 - th^2) / Sm - p r / Sm^2) / tw for every t.
+ * individual: the forward recurrence is recomputed (ws[B*c*tw] doubles receive p_i; ws may be NULL for block), then
+ * from i = tw - 1 down with lambda = 0: a = D_i / s_i + lambda, c_i = -D_i r_i p_i / s_i^2 + a (1 - th_i^2),
+ * lambda = a (r_i - (1 - th_i^2) s_i / p_i). */
+int nps_volume_factors_bwd(const double* new_tot, const double* prev_tot, const double* D, int mode,
+                           double max_pct_dif, double* ws, float* c, int B, int num_c, int tw, void* stream);
+/* in place: u[plane] *= F[plane], then u -= mask[b][mask_ch] u (mask (B, mask_S, H, W) or NULL) */
+int nps_volume_apply(float* u, const float* F, const float* mask, int mask_S, int mask_ch, int B, int num_c, int tw,
+                     int H, int W, void* stream);
+/* gu[plane] = g (1 - mask[b][mask_ch]) F[plane] + c[plane] */
+int nps_volume_apply_bwd(const float* g, const float* F, const float* c, const float* mask, int mask_S, int mask_ch,
+                         float* gu, int B, int num_c, int tw, int H, int W, void* stream);
+
 /* ---- grid decoders: the per-pixel Conv1d chain + add_delta + tanh + mask (csrc/decode_chain.hip) ----
  * One entry for dec_grid.TimeConvLinear (one stage), TimeConv and TimeConvDense with dec_delta_mode 'all' / 'none'
  * (two stages), and LinearConv's epilogue / add_delta itself (no stage); dec_grid.py:8-31, :34-195.

@@ -2,8 +2,9 @@
 
 Returns an instance of a dynamic subclass `ActWrapper-<model_class>` exactly
 like the reference.  On the MI355X path the final tanh and the spatial-cond
-mask run inside the decoder kernel; 'individual_static' volume preservation
-is two fp64 plane-sum reductions + one element-wise rescale/mask kernel.
+mask run inside the decoder kernel; volume preservation is two fp64 plane-sum
+reductions + one element-wise rescale/mask kernel ('individual_static'), or,
+for 'block' and 'individual', a per-(b, c) fp64 factor kernel in between.
 """
 import numpy as np
 import torch
@@ -41,6 +42,8 @@ def activation_wrapper(model_class: str, activation_final: nn.Module, enforce_sp
                                       f"{nd}-D (spatial_cond as input channels works in every dimension)")
         if nd != 2 and approx_volume_preserve:
             raise ValueError(f"{nd} spatial dims not supported for approx volume preserve")  # :52, :78, :100
+        if approx_volume_preserve and approx_volume_preserve_mode not in ('block', 'individual', 'individual_static'):
+            raise ValueError(f"Unrecognized approx_volume_preserve_mode '{approx_volume_preserve_mode}'")  # :103
         x = b["x"] if "x" in b else a[0]
         fwd_kw = dict(b)
         fwd_kw.pop("x", None)
@@ -53,22 +56,26 @@ def activation_wrapper(model_class: str, activation_final: nn.Module, enforce_sp
         u = self.forward_fused(x, final_tanh=True,
                                mask_channel=spatial_cond_channel if enforce_spatial_cond else None, **fwd_kw)
         if approx_volume_preserve:
-            if approx_volume_preserve_mode != 'individual_static':
-                raise NotImplementedError(
-                    f"approx_volume_preserve_mode '{approx_volume_preserve_mode}' is not on the MI355X path "
-                    "(twophase cfgs use 'individual_static')")
             B, c, tw, H, W = u.shape
+            static = approx_volume_preserve_mode == 'individual_static'  # :80-101; else 'block' :40-53, 'individual' :54-79
             key = (float(max_pct_dif), tw, str(u.device))
-            if getattr(self, "_mpd_key", None) != key:
+            if static and getattr(self, "_mpd_key", None) != key:
                 self._mpd_tab = torch.from_numpy(_mpd_cumsum(max_pct_dif, tw)).to(u.device)
                 self._mpd_key = key
             mask = sc.float().contiguous() if enforce_spatial_cond else None
             if u.requires_grad:
-                return ad.VolumeRescaleFn.apply(spatial_cond_channel, u, x.detach(), self._mpd_tab, mask)
+                if static:
+                    return ad.VolumeRescaleFn.apply(spatial_cond_channel, u, x.detach(), self._mpd_tab, mask)
+                meta = (spatial_cond_channel, approx_volume_preserve_mode, float(max_pct_dif))
+                return ad.VolumeModeFn.apply(meta, u, x.detach(), mask)
             xc = x.contiguous()
             new_tot = ops.plane_sums(u, 0, H * W, H * W, B * c * tw)                        # :81
             prev_tot = ops.plane_sums(xc, (xc.shape[2] - 1) * H * W, xc.shape[2] * H * W, H * W, B * c)  # :84
-            ops.volume_rescale(u, new_tot, prev_tot, self._mpd_tab, mask, spatial_cond_channel)
+            if static:
+                ops.volume_rescale(u, new_tot, prev_tot, self._mpd_tab, mask, spatial_cond_channel)
+            else:
+                F = ops.volume_factors(new_tot, prev_tot, approx_volume_preserve_mode, max_pct_dif, B, c, tw)
+                ops.volume_apply(u, F, mask, spatial_cond_channel)
         return u
 
     return type(f'ActWrapper-{model_class}', (modeltype,), {'forward': new_forward})(*args, **kwargs)

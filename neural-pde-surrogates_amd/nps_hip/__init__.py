@@ -206,6 +206,11 @@ _SIGS = {
     "nps_decode_bwd": (_i, [ctypes.POINTER(DecodeArgs)] + [_vp] * 8),
     "nps_plane_dot": (_i, [_vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _vp, _vp]),
     "nps_volume_rescale_bwd": (_i, [_vp, _vp, _vp, _vp, _vp, _i, _i, _vp, _vp, _i, _i, _i, _i, _i, _vp]),
+    # approx_volume_preserve 'block' / 'individual' (max_pct_dif is a double)
+    "nps_volume_factors": (_i, [_vp, _vp, _i, ctypes.c_double, _vp, _i, _i, _i, _vp]),
+    "nps_volume_factors_bwd": (_i, [_vp, _vp, _vp, _i, ctypes.c_double, _vp, _vp, _i, _i, _i, _vp]),
+    "nps_volume_apply": (_i, [_vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _i, _vp]),
+    "nps_volume_apply_bwd": (_i, [_vp, _vp, _vp, _vp, _i, _i, _vp, _i, _i, _i, _i, _i, _vp]),
     # one call per module (composites of the spectral stages)
     "nps_spectral_conv2d_workspace": (_sz, [_i] * 7),
     "nps_spectral_conv2d_fwd": (_i, [_vp] * 5 + [_i] * 9 + [_vp]),

@@ -1322,6 +1322,46 @@ class VolumeRescaleFn(torch.autograd.Function):
         return None, gu, None, None, None
 
 
+class VolumeModeFn(torch.autograd.Function):
+    """activation_wrapper 'block' / 'individual' volume preservation + re-applied mask (activation_wrapper.py:40-79);
+    meta = (mask_ch, mode, max_pct_dif).  x (the model input) is data and gets no gradient."""
+
+    @staticmethod
+    def forward(ctx, meta, u, x, mask):
+        mask_ch, mode, m = meta
+        u = _c(u)
+        B, c, tw, H, W = u.shape
+        xc = _c(x)
+        new_tot = ops.plane_sums(u, 0, H * W, H * W, B * c * tw)
+        prev_tot = ops.plane_sums(xc, (xc.shape[2] - 1) * H * W, xc.shape[2] * H * W, H * W, B * c)
+        F = ops.volume_factors(new_tot, prev_tot, mode, m, B, c, tw)
+        out = ops.volume_apply(u.clone(), F, mask, mask_ch)
+        ctx.meta = meta
+        ctx.has_mask = mask is not None
+        ctx.save_for_backward(u, new_tot, prev_tot, F, mask if mask is not None else torch.empty(0))
+        return out
+
+    @staticmethod
+    def backward(ctx, g):
+        mask_ch, mode, m = ctx.meta
+        u, new_tot, prev_tot, F, mask = ctx.saved_tensors
+        mask = mask if ctx.has_mask else None
+        g = _c(g)
+        B, c, tw, H, W = u.shape
+        S = 0 if mask is None else mask.shape[1]
+        D = torch.empty(B * c * tw, dtype=torch.float64, device=g.device)
+        check(lib.nps_plane_dot(ptr(g), ptr(u), ptr(mask), S, mask_ch, B, c * tw, H, W, ptr(D), stream_ptr()),
+              "plane_dot")
+        ws = torch.empty_like(D) if mode == "individual" else None  # p_i of the recomputed recurrence
+        coef = torch.empty_like(F)
+        check(lib.nps_volume_factors_bwd(ptr(new_tot), ptr(prev_tot), ptr(D), ops.VOLUME_MODES[mode], float(m),
+                                         ptr(ws), ptr(coef), B, c, tw, stream_ptr()), "volume_factors_bwd")
+        gu = torch.empty_like(u)
+        check(lib.nps_volume_apply_bwd(ptr(g), ptr(F), ptr(coef), ptr(mask), S, mask_ch, ptr(gu), B, c, tw, H, W,
+                                       stream_ptr()), "volume_apply_bwd")
+        return None, gu, None, None
+
+
 class SqrtMseSumFn(torch.autograd.Function):
     """torch.sqrt(nn.MSELoss(reduction='sum')(pred, labels)) — autoregressivepushforwardtrainer.py:158-162."""
 

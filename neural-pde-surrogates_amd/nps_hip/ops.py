@@ -1833,6 +1833,26 @@ def volume_rescale(u, new_tot, prev_tot, mpdcum, mask, mask_ch):
     return u
 
 
+VOLUME_MODES = {"block": 0, "individual": 1}  # NPS_VOLUME_* of include/nps.h
+
+
+def volume_factors(new_tot, prev_tot, mode: str, max_pct_dif: float, B: int, c: int, tw: int) -> torch.Tensor:
+    """F (B, c, tw) of approx_volume_preserve_mode 'block' / 'individual' (activation_wrapper.py:40-79) from the fp64
+    plane totals of u and of the input's last time step; the scalars stay fp64 on the device."""
+    F = torch.empty(B, c, tw, dtype=torch.float32, device=new_tot.device)
+    check(lib.nps_volume_factors(ptr(new_tot), ptr(prev_tot), VOLUME_MODES[mode], float(max_pct_dif), ptr(F), B, c,
+                                 tw, stream_ptr()), "volume_factors")
+    return F
+
+
+def volume_apply(u, F, mask, mask_ch):
+    """In place: u[b, c, t] *= F[b, c, t], then the spatial-cond mask re-applied (activation_wrapper.py:104-105)."""
+    B, c, tw, H, W = u.shape
+    S = 0 if mask is None else mask.shape[1]
+    check(lib.nps_volume_apply(ptr(u), ptr(F), ptr(mask), S, mask_ch, B, c, tw, H, W, stream_ptr()), "volume_apply")
+    return u
+
+
 def sq_err_sum(a: torch.Tensor, b: torch.Tensor) -> torch.Tensor:
     a = a.contiguous()
     b = b.contiguous()
