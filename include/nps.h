@@ -764,7 +764,7 @@ int nps_conv3d_fwd(const nps_conv3d_t* a, void* stream);
 int nps_conv3d_route(const nps_conv3d_t* a, char* buf, int n);
 int nps_conv3d_1x1_set_grid(long wgs);
 /* act(GN(frame)) of a's core frame (sources, GroupNorm prologue, pre_act) materialised once as
- * out[B][Dc][Hc][Wc][Cpad] (channels >= Cin zero, Cpad % 8 == 0): the conv that follows reads one aligned
+ * out[B][Dc][Hc][Wc][Cpad] (channels >= Cin zero, Cpad % 8 == 0, Cpad <= 1024): the conv that follows reads one aligned
  * source without a prologue (the fused prologue recomputes each element for every depth tap and halo). */
 int nps_frame_pack3d(const nps_conv3d_t* a, void* out, int Cpad, void* stream);
 /* GroupNorm moments of a core frame (a's sources and B, Dc, Hc, Wc, Cin, bf16): ADDS per (b, group) the

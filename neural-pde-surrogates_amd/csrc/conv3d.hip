@@ -763,10 +763,11 @@ __global__ __launch_bounds__(256) void gn_stats3d_kernel(const nps_conv3d_t a, i
 // per frame element (the fused prologue would apply it to every element K x ~1.3 times, once per depth tap
 // and halo); the conv then reads a single 16-channel-aligned source (conv3d_kernel SIMPLE).  One item = 8
 // channels of one voxel (16-B loads / stores for bf16).
+constexpr int PACK3D_MAX_C = 1024;  // (the table below; nps_frame_pack3d refuses a wider frame)
 template <typename T>
 __global__ __launch_bounds__(256) void frame_pack3d_kernel(const nps_conv3d_t a, T* __restrict__ out, int Cpad,
                                                            bool mflat_disabled) {
-    __shared__ __attribute__((aligned(16))) float scl[512], sft[512];
+    __shared__ __attribute__((aligned(16))) float scl[PACK3D_MAX_C], sft[PACK3D_MAX_C];
     const int b = blockIdx.y;
     const bool gn = a.gn_stats != nullptr;
     for (int c = threadIdx.x; c < Cpad; c += 256) {
@@ -1401,7 +1402,8 @@ extern "C" int nps_frame_pack3d(const nps_conv3d_t* ap, void* out, int Cpad, voi
     NPS_CHECK_ARG(ap != nullptr && out != nullptr, "frame_pack3d: null args");
     const nps_conv3d_t& a = *ap;
     if (check_frame(a, "frame_pack3d") < 0) return -1;
-    NPS_CHECK_ARG(Cpad >= a.Cin && Cpad % 8 == 0 && Cpad <= 512, "frame_pack3d: Cpad %d (>= Cin, %% 8, <= 512)", Cpad);
+    NPS_CHECK_ARG(Cpad >= a.Cin && Cpad % 8 == 0 && Cpad <= PACK3D_MAX_C, "frame_pack3d: Cpad %d (>= Cin, %% 8, <= %d)",
+                  Cpad, PACK3D_MAX_C);
     NPS_CHECK_ARG(a.gn_stats == nullptr || (a.gn_gamma && a.gn_beta && a.gn_groups >= 1 && a.Cin % a.gn_groups == 0),
                   "frame_pack3d: bad GroupNorm prologue");
     const long nitem = (long)a.Dc * a.Hc * a.Wc * (Cpad / 8);

@@ -46,12 +46,6 @@ def _whole_frame(srcs, size):
     return len(srcs) == 1 and not any(srcs[0][1:]) and tuple(srcs[0].t.shape[1:1 + len(size)]) == tuple(size)
 
 
-def _check_identity_input(srcs, size):
-    """The 3-D forms' identity shortcut adds x itself: one source that is the whole frame."""
-    if not _whole_frame(srcs, size):
-        raise RuntimeError("identity shortcut on a concatenated input")
-
-
 def _res_attn(form, m, res, srcs, size):
     """m.attn(res(frame of srcs)) of a Down / Middle / Up block m in the given form."""
     if isinstance(m.attn, nn.Identity):
@@ -360,10 +354,22 @@ class ResidualBlock(nn.Module):
         carry_out = ops.CARRY3D and isinstance(self.norm1, nn.GroupNorm)
         st_out = None
         if isinstance(self.shortcut, nn.Identity):
-            _check_identity_input(srcs, frame_dhw)
-            out = srcs[0].t.clone()
-            if carry_out:
-                st_out = ops.copy_stats(ops.source_stats3d(srcs[0].t))
+            if _whole_frame(srcs, frame_dhw):
+                out = srcs[0].t.clone()
+                if carry_out:
+                    st_out = ops.copy_stats(ops.source_stats3d(srcs[0].t))
+            elif srcs[0].t.dtype != torch.float32:
+                raise NotImplementedError("ResidualBlock.run3d: an identity shortcut on a concatenated input "
+                                          "(in_channels with the conditioning / skip channels == out_channels) runs "
+                                          "in fp32 storage only")
+            else:
+                # in_channels (with the conditioning / skip channels) == out_channels: the identity adds the
+                # concatenation itself (e.g. hidden 16 + n_cond 16 -> 32), materialised once by nps_frame3d_fwd
+                out = ops.frame3d(srcs, frame_dhw)
+                if carry_out:
+                    # the frame's moments are the sum of its sources' (zero crop padding adds nothing), as norm1
+                    # took them above: the next norm1 needs no pass
+                    st_out = ops.copy_stats(ops.group_norm_stats3d(srcs, frame_dhw, 1))
         else:
             st_out = ops.new_stats(B, srcs[0].t) if carry_out else None
             out = self.shortcut.run3d(srcs, frame_dhw, out_stats=st_out)
@@ -401,10 +407,9 @@ class ResidualBlock(nn.Module):
         act = activation_code(self.activation)
         n1 = self.norm1 if isinstance(self.norm1, nn.GroupNorm) else None
         n2 = self.norm2 if isinstance(self.norm2, nn.GroupNorm) else None
-        if isinstance(self.shortcut, nn.Identity):
-            _check_identity_input(srcs, frame_dhw)
         f1, xin = ad.frame_pair3d(srcs, frame_dhw, n1, act)
         h1 = ad.conv3d(self.conv1, f1)
+        # (the identity adds x itself, or the plain concatenation the frame pair materialised)
         sc = xin if isinstance(self.shortcut, nn.Identity) else ad.conv3d(self.shortcut, xin)
         h2 = ad.conv3d(self.conv2, ad.frame3d([ops.Src3(h1)], h1.shape[1:4], n2, act))
         return ad.add_at3d(sc, h2, crop_offsets(h2.shape[1:4], sc.shape[1:4]))

@@ -463,7 +463,12 @@ FRAME_CASES = [FrameCase("f853_inside", _INSIDE(_PA), (4, 6, 11)), FrameCase("f8
                FrameCase("f484_inside", _INSIDE(_PB), (4, 6, 11)), FrameCase("f484_crop", _PB, (4, 6, 11)),
                # C % 8 == 4 and C % 4 != 0 single sources
                FrameCase("f20_single", ((20, 4, 6, 11, 0, 0, 0),), (4, 6, 11)),
-               FrameCase("f12_single_crop", ((12, 6, 4, 9, -1, 1, 2),), (4, 6, 11))]
+               FrameCase("f12_single_crop", ((12, 6, 4, 9, -1, 1, 2),), (4, 6, 11)),
+               # 516 channels, packed to 528 > 512 (the up-block frame of a hidden-64 U-Net with ch_mults (2, 2) and
+               # n_cond 4): past the one-thread-per-piece kernel's 64 pieces; whole sources, and skip / vb zero-padded in
+               FrameCase("f516_inside", tuple((C, 3, 4, 5, 0, 0, 0) for C in (256, 256, 4)), (3, 4, 5)),
+               FrameCase("f516_crop", ((256, 3, 4, 5, 0, 0, 0), (256, 2, 3, 4, 0, 1, 1), (4, 2, 3, 3, 1, 0, 2)),
+                         (3, 4, 5))]
 FRAME_BY_NAME = {c.name: c for c in FRAME_CASES}
 
 

@@ -41,11 +41,15 @@ class Row(NamedTuple):
 UFNO_BLOCKS, UFNO_MODES = 2, 4
 
 
+def row_id(kind, hidden, ch_mults, n_blocks, pm, norm, use1x1, n_cond, size, B):
+    """The id scheme of a matrix row, shared with tests/unet3d_matrix.py (`size` = the grid, any rank)."""
+    return (f"{kind}-h{hidden}-m{''.join(map(str, ch_mults))}-b{n_blocks}-{pm[:4]}-{'gn' if norm else 'nogn'}-"
+            f"{'k1' if use1x1 else 'k3'}-c{n_cond}-{'x'.join(map(str, size))}-B{B}")
+
+
 def _row(kind, hidden, ch_mults, n_blocks, pm, norm, use1x1, n_cond, hw, B):
     c = Case(hidden, tuple(ch_mults), n_blocks, pm, norm, use1x1, n_cond, tuple(hw), B)
-    rid = (f"{kind}-h{hidden}-m{''.join(map(str, ch_mults))}-b{n_blocks}-{pm[:4]}-{'gn' if norm else 'nogn'}-"
-           f"{'k1' if use1x1 else 'k3'}-c{n_cond}-{hw[0]}x{hw[1]}-B{B}")
-    return Row(rid, kind, c)
+    return Row(row_id(kind, *c), kind, c)
 
 
 def _core_rows():
@@ -159,45 +163,46 @@ def randomise_(sd: dict, g: torch.Generator):
     return sd
 
 
-def _conv_entries(sd, key, cout, cin, k, g, transposed=False):
-    bound = 1.0 / math.sqrt((cout if transposed else cin) * k * k)  # nn.Conv2d's default: U(+-1/sqrt(fan_in))
-    shape = (cin, cout, k, k) if transposed else (cout, cin, k, k)
+def _conv_entries(sd, key, cout, cin, k, g, transposed=False, nd=2):
+    bound = 1.0 / math.sqrt((cout if transposed else cin) * k ** nd)  # nn.ConvNd's default: U(+-1/sqrt(fan_in))
+    shape = ((cin, cout) if transposed else (cout, cin)) + (k,) * nd
     sd[key + ".weight"] = (torch.rand(shape, generator=g) * 2 - 1) * bound
     sd[key + ".bias"] = torch.zeros(cout)
 
 
-def _res_entries(sd, p, cin, cout, norm, g):
+def _res_entries(sd, p, cin, cout, norm, g, nd=2):
     if norm:
         for n, c in (("norm1", cin), ("norm2", cout)):
             sd[f"{p}.{n}.weight"], sd[f"{p}.{n}.bias"] = torch.ones(c), torch.zeros(c)
-    _conv_entries(sd, p + ".conv1", cout, cin, 3, g)
-    _conv_entries(sd, p + ".conv2", cout, cout, 3, g)
+    _conv_entries(sd, p + ".conv1", cout, cin, 3, g, nd=nd)
+    _conv_entries(sd, p + ".conv2", cout, cout, 3, g, nd=nd)
     if cin != cout:
-        _conv_entries(sd, p + ".shortcut", cout, cin, 1, g)
+        _conv_entries(sd, p + ".shortcut", cout, cin, 1, g, nd=nd)
 
 
-def _unet_entries(sd, p, c: Case, g):
+def _unet_entries(sd, p, c, g, nd=2):
     """The state_dict keys and shapes of UNetModern (reference proc_unet_modern.py:91-152) from
-    oracle.functional.unet_structure; `p` = key prefix with its trailing dot."""
+    oracle.functional.unet_structure; `p` = key prefix with its trailing dot, `nd` = the convs' spatial rank (`c` is
+    this file's Case or the 3-D matrix's: only the fields both have are read)."""
     down, _, up = Fo.unet_structure(c.hidden, c.ch_mults, c.n_blocks, c.n_cond)
     for i, m in enumerate(down):
         if m[0] == "down":
-            _res_entries(sd, f"{p}down.{i}.res", m[1], m[2], c.norm, g)
+            _res_entries(sd, f"{p}down.{i}.res", m[1], m[2], c.norm, g, nd)
         else:
-            _conv_entries(sd, f"{p}down.{i}.conv", m[1], m[1], 3, g)
+            _conv_entries(sd, f"{p}down.{i}.conv", m[1], m[1], 3, g, nd=nd)
             if c.n_cond > 0:
-                _conv_entries(sd, f"{p}down.{i}.conv_variables_broadcast", c.n_cond, c.n_cond, 3, g)
+                _conv_entries(sd, f"{p}down.{i}.conv_variables_broadcast", c.n_cond, c.n_cond, 3, g, nd=nd)
     top = c.hidden * math.prod(c.ch_mults)
-    _res_entries(sd, f"{p}middle.res1", top + c.n_cond, top, c.norm, g)
-    _res_entries(sd, f"{p}middle.res2", top, top, c.norm, g)
+    _res_entries(sd, f"{p}middle.res1", top + c.n_cond, top, c.norm, g, nd)
+    _res_entries(sd, f"{p}middle.res2", top, top, c.norm, g, nd)
     for i, m in enumerate(up):
         if m[0] == "up":  # UpBlock(cin, cout).res = ResidualBlock(cin + cout, cout): the skip has cout channels
-            _res_entries(sd, f"{p}up.{i}.res", m[1] + m[2], m[2], c.norm, g)
+            _res_entries(sd, f"{p}up.{i}.res", m[1] + m[2], m[2], c.norm, g, nd)
         else:
-            _conv_entries(sd, f"{p}up.{i}.conv", m[1], m[1], 4, g, transposed=True)
+            _conv_entries(sd, f"{p}up.{i}.conv", m[1], m[1], 4, g, transposed=True, nd=nd)
     if c.norm:
         sd[p + "norm.weight"], sd[p + "norm.bias"] = torch.ones(c.hidden), torch.zeros(c.hidden)
-    _conv_entries(sd, p + "final", c.hidden, c.hidden, 1 if c.use1x1 else 3, g)
+    _conv_entries(sd, p + "final", c.hidden, c.hidden, 1 if c.use1x1 else 3, g, nd=nd)
 
 
 def standin_state_dict(row: Row) -> dict:
@@ -240,11 +245,15 @@ def build_module(row: Row):
 # ------------------------------------------------------------------------------------------- inputs / reference
 def inputs(row: Row):
     """(h, vb or None, gy): float32, h and vb uniform in [-1, 1], gy standard normal, seeded per row."""
-    c = row.case
-    g = torch.Generator().manual_seed(5000 + _seed(row))
-    h = torch.rand(c.B, c.hidden, *c.hw, generator=g) * 2 - 1
-    vb = torch.rand(c.B, c.n_cond, *c.hw, generator=g) * 2 - 1 if c.n_cond > 0 else None
-    gy = torch.randn(c.B, c.hidden, *c.hw, generator=g)
+    return seeded_inputs(row.case, row.case.hw, 5000 + _seed(row))
+
+
+def seeded_inputs(c, size, seed):
+    """inputs() of a case on the grid `size` (any rank) from one seeded generator: h, vb, gy in that order."""
+    g = torch.Generator().manual_seed(seed)
+    h = torch.rand(c.B, c.hidden, *size, generator=g) * 2 - 1
+    vb = torch.rand(c.B, c.n_cond, *size, generator=g) * 2 - 1 if c.n_cond > 0 else None
+    gy = torch.randn(c.B, c.hidden, *size, generator=g)
     return h, vb, gy
 
 
@@ -265,17 +274,22 @@ def _cast(t, dtype):
 
 def reference(row: Row, sd: dict, h, vb, gy=None, dtype=torch.float64) -> Ref:
     """The oracle on the `dtype` copy of sd and the inputs; with gy also dh, dvb and every parameter gradient."""
+    return oracle_reference(oracle_fn(row), oracle_cfg(row), sd, h, vb, gy, dtype)
+
+
+def oracle_reference(fn, cfg, sd: dict, h, vb, gy=None, dtype=torch.float64) -> Ref:
+    """reference() for the oracle function `fn` and its cfg (tests/unet3d_matrix.py passes the 3-D ones)."""
     sd = {k: _cast(v.detach().cpu(), dtype).clone() for k, v in sd.items()}
     h, vb = _cast(h, dtype).clone(), _cast(vb, dtype)
     if gy is None:
         with torch.no_grad():
-            return Ref(oracle_fn(row)(sd, "", oracle_cfg(row), h, vb), None, None, None)
+            return Ref(fn(sd, "", cfg, h, vb), None, None, None)
     for t in sd.values():
         t.requires_grad_(True)
     h.requires_grad_(True)
     if vb is not None:
         vb = vb.clone().requires_grad_(True)
-    y = oracle_fn(row)(sd, "", oracle_cfg(row), h, vb)
+    y = fn(sd, "", cfg, h, vb)
     y.backward(_cast(gy, dtype))
     return Ref(y.detach(), h.grad, vb.grad if vb is not None else None, {k: t.grad for k, t in sd.items()})
 
